@@ -8,16 +8,22 @@ on device).  One step = for every client a top-k (f = 0.1) encode into a device 
 + gar.py:44, bit-exact fp32), then — with N > 1 GPUs — one RCCL fp32 reduce of the partial
 aggregate to rank 0.  Weak scaling: per-GPU work is fixed.
 
-    python bench.py [--gpus 1] [--steps 10] [--warmup 2]
+    python bench.py [--gpus 1] [--steps 10] [--warmup 2] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N ... bench.py --gpus N       (one process per GPU, RCCL)
 
 Prints ONE JSON line on rank 0.  `value` = gradient bytes (4 N per client, all ranks) per
-second of step time; `roofline` = the encode pass k_compact_mag1 (the dominant kernel), algorithmic
-bytes 4N + 8k per client (ABI-3 packets write 6 B per entry) over its HIP-event-timed average launch duration, `traffic` from the
-committed calibrated PMC summary; `cpu_baseline` = the reference's exact NumPy calls
-(compression.py:31-37, default argsort) on one 128 M gradient, with every BASELINE.md §3 row
-in `extra.cpu_baseline_matrix`.  A self-check outside the timed region re-encodes two clients
-alone and compares them bit for bit with the batch.
+second of step time, `ms_per_step` = the milliseconds one timed step took; `roofline` = the
+encode pass k_compact_mag1 (the dominant kernel), algorithmic bytes 4N + 8k per client
+(ABI-3 packets write 6 B per entry) over its HIP-event-timed average launch
+duration in the timed steps, `traffic` from the committed calibrated PMC summary.
+
+A plain run sets up, warms up, times the steps, writes the last step's outputs when
+`--dump-outputs DIR` is given (`dump_outputs`) and prints the line.  Everything else runs only
+with `--full`: `cpu_baseline` = the reference's exact NumPy calls (compression.py:31-37,
+default argsort) on one 128 M gradient, with every BASELINE.md §3 row in
+`extra.cpu_baseline_matrix`; the single-gradient probes, configs[1]/[2] and the codec matrix;
+the one-stream roofline passes of a `--streams` > 1 run; and a self-check outside the timed
+region that re-encodes two clients alone and compares them bit for bit with the batch.
 """
 from __future__ import annotations
 
@@ -55,10 +61,19 @@ def parse():
     ap.add_argument("--tag", default=None, help="A/B only: a label echoed in the JSON line")
     ap.add_argument("--backend", default="nccl", choices=("nccl", "gloo"),
                     help="nccl (RCCL over xGMI: the measurement) or gloo (rehearsal only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-single", action="store_true", help="skip the single-gradient probe")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the self-check, the CPU baselines, the "
+                         "single-gradient probes, configs[1]/[2], the codec matrix and the "
+                         "one-stream roofline passes (a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the last timed step's outputs to DIR/<name>.npy "
+                         "(dump_outputs: a fixed seeded sample, float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-single", action="store_true",
+                    help="with --full: skip the single-gradient probes and configs[1]/[2]")
     ap.add_argument("--no-matrix", action="store_true",
-                    help="skip the SURVEY §8(d) codec matrix (extra.codec_matrix)")
+                    help="with --full: skip the SURVEY §8(d) codec matrix (extra.codec_matrix)")
     ap.add_argument("--pipeline", action="store_true",
                     help="fold each encode chain's packets on its stream as soon as they are "
                          "encoded (codec.encode_fold_batch; measured no faster, A/B only)")
@@ -291,6 +306,36 @@ def load_pmc(path):
         return None, None
 
 
+DUMP_SAMPLE = 2_097_152         # entries per dumped array: 4 arrays stay below 64 MB in all
+DUMP_SEED = 20240607
+
+
+def dump_outputs(out_dir, torch, codec, acc, pkts, n):
+    """What the last timed step handed back, as ``out_dir/<name>.npy``: the FedAVG aggregate
+    (``aggregate``, float32) and the first and the last client's packet in its dense form
+    (``client_first_decoded`` / ``client_last_decoded``, float32: compression.py:31-37's q).
+    An array longer than DUMP_SAMPLE is sampled at fixed positions (np.random.default_rng(
+    DUMP_SEED), sorted, the same for every run at one n), listed in ``sample_index`` (float64,
+    exact below 2**53)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    if n > DUMP_SAMPLE:
+        pos = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, size=DUMP_SAMPLE))
+    else:
+        pos = np.arange(n, dtype=np.int64)
+    at = torch.from_numpy(pos).to(acc.device)
+
+    def save(name, t):
+        np.save(os.path.join(out_dir, name + ".npy"),
+                np.ascontiguousarray(t[at].cpu().numpy(), dtype=np.float32))
+
+    save("aggregate", acc)
+    dense = torch.empty(n, dtype=torch.float32, device=acc.device)
+    for name, p in (("client_first_decoded", pkts[0]), ("client_last_decoded", pkts[-1])):
+        save(name, codec.decode(p, out=dense))
+    np.save(os.path.join(out_dir, "sample_index.npy"), pos.astype(np.float64))
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -428,13 +473,15 @@ def main():
     if args.dump_agg and rank == 0:
         import numpy as np
         np.save(args.dump_agg, accs[(nstep[0] - 1) & 1].cpu().numpy())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, torch, codec, accs[(nstep[0] - 1) & 1], pkts, n)
     if pg:                                          # exact re-encodes over all ranks
         t = torch.tensor([redo_total[0]], dtype=torch.int64,
                          device=device if args.backend == "nccl" else "cpu")
         dist.all_reduce(t)
         redo_total[0] = int(t.item())
     # the packets of the last timed step against single-client encodes, before anything reuses them
-    checked = self_check(torch, codec, grads, pkts, k, last_redo)
+    checked = self_check(torch, codec, grads, pkts, k, last_redo) if args.full else None
     grad_bytes = 4.0 * n * M * world
     value = grad_bytes / (elapsed / args.steps) / 1e9
 
@@ -445,7 +492,7 @@ def main():
     # In a rocprofv3 trace these are the k_compact_mag1 dispatches with grid.y == per_launch
     # (tools/rocpd_summary.py stats splits dispatches by grid).
     kt_roof = kt
-    if args.roofline_steps > 0 and not args.no_batch and args.streams > 1:
+    if args.full and args.roofline_steps > 0 and not args.no_batch and args.streams > 1:
         torch.cuda.synchronize()
         with L.KernelTimer(L.FC_TIME_COMPACT) as kt_roof:
             for _ in range(args.roofline_steps):
@@ -486,7 +533,7 @@ def main():
         extra["tag"] = args.tag
     extra["process_group"] = ({"backend": args.backend, "world": world,
                                "collective_per_step": "reduce (async)"} if pg else None)
-    if rank == 0 and not args.no_single:
+    if args.full and rank == 0 and not args.no_single:
         extra["single_gradient"] = single_gradient(torch, codec, grads[0], k, n, graph=not pg)
         extra["qsgd_single_gradient"] = qsgd_single(torch, codec, grads[0], n)
 
@@ -494,13 +541,13 @@ def main():
     # headline workload's buffers are released
     del grads, pkts, jobs, views, fold, hdrs
     torch.cuda.empty_cache()
-    if world == 1 and rank == 0 and not args.no_single:
+    if args.full and world == 1 and rank == 0 and not args.no_single:
         extra["configs_1_2"] = small_configs(torch, codec, L, device, f, graph=not pg)
-    if world == 1 and rank == 0 and not args.no_matrix:
+    if args.full and world == 1 and rank == 0 and not args.no_matrix:
         extra["codec_matrix"] = codec_matrix(torch, codec, L, device)
 
     cpu = None
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         cpu = cpu_baseline(n, f)
         mat = cpu_matrix()
         t_client = 4.0 * n / (cpu["value"] * 1e9)

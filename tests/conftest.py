@@ -10,6 +10,10 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 GOLDEN_DIR = os.path.join(ROOT, "tests", "golden")
+if GOLDEN_DIR not in sys.path:
+    sys.path.append(GOLDEN_DIR)
+
+from npz_parts import load_parts  # noqa: E402  (tests/golden/npz_parts.py)
 
 
 def pytest_configure(config):
@@ -20,7 +24,7 @@ class Golden:
     def __init__(self):
         with open(os.path.join(GOLDEN_DIR, "manifest.json")) as fh:
             self.manifest = json.load(fh)
-        self.arrays = np.load(os.path.join(GOLDEN_DIR, "golden_codec.npz"))
+        self.arrays = load_parts(GOLDEN_DIR, "golden_codec")
 
     def cases(self, prefix=""):
         return sorted(k for k in self.manifest["cases"] if k.startswith(prefix))
@@ -66,7 +70,7 @@ class AggGolden:
     def __init__(self):
         with open(os.path.join(GOLDEN_DIR, "manifest_agg.json")) as fh:
             self.manifest = json.load(fh)
-        self.arrays = np.load(os.path.join(GOLDEN_DIR, "golden_agg.npz"))
+        self.arrays = load_parts(GOLDEN_DIR, "golden_agg")
 
     def cases(self, prefix=""):
         return sorted(k for k in self.manifest["cases"] if k.startswith(prefix))

@@ -17,6 +17,8 @@ import sys
 
 import numpy as np
 
+from npz_parts import save_parts
+
 sys.dont_write_bytecode = True
 REF = "/root/reference"
 OUT = os.path.dirname(os.path.abspath(__file__))
@@ -164,7 +166,7 @@ def main():
         del g, q, nz
     manifest["large"] = large
 
-    np.savez_compressed(os.path.join(OUT, "golden_codec.npz"), **arrays)
+    save_parts(OUT, "golden_codec", arrays)           # golden_codec.NN.npz, each below 1 MiB
     with open(os.path.join(OUT, "manifest.json"), "w") as fh:
         json.dump(manifest, fh, indent=1, sort_keys=True)
     print(f"wrote {len(manifest['cases'])} cases, {len(large)} large digests")

@@ -9,7 +9,7 @@ and records inputs and outputs of
   * ``Aggregator.__merge_gradient`` (aggregation.py:80-93) followed by ``FedAvg.aggregate``
     (the ``num_hierarchies > 0`` branch of aggregation.py:68-75), one and two stages, with a
     remainder absorbed by the last cluster.
-Only data is written (``golden_agg.npz`` + ``manifest_agg.json``).
+Only data is written (``golden_agg.NN.npz`` + ``manifest_agg.json``).
 """
 from __future__ import annotations
 
@@ -18,6 +18,8 @@ import os
 import sys
 
 import numpy as np
+
+from npz_parts import save_parts
 
 sys.dont_write_bytecode = True
 REF = "/root/reference"
@@ -78,7 +80,7 @@ def main():
         add(f"hier__M{M}__n{n}__c{'-'.join(map(str, sizes))}", M=M, n=n,
             cluster_size_list=sizes, G=G, merged=H, output=agg)
 
-    np.savez_compressed(os.path.join(OUT, "golden_agg.npz"), **arrays)
+    save_parts(OUT, "golden_agg", arrays)           # golden_agg.NN.npz, each below 1 MiB
     with open(os.path.join(OUT, "manifest_agg.json"), "w") as fh:
         json.dump({"cases": cases}, fh, indent=1, sort_keys=True)
     print(f"wrote {len(cases)} aggregation cases")

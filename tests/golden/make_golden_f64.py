@@ -7,7 +7,7 @@ float64 gradients reach the codec after RandomGaussian with noise_scale == 0
 estimators set float64 ``gradient_weights`` on the GAR (aggregation.py:181-198), which promotes
 ``G * w`` (gar.py:44) to float64 for a float32 G too.  This script imports OpenMSFTL from
 /root/reference (``import ftl.agents`` first) and records, as data only
-(``golden_f64.npz`` + ``manifest_f64.json``):
+(``golden_f64.NN.npz`` + ``manifest_f64.json``):
   * ``Compression.compress`` on float64 inputs: top / rand / dropout-* (seeded legacy RNG, the
     RNG state after the call), ties, +-0, NaN/inf;
   * ``Aggregator.aggregate_grads`` (aggregation.py:54-78) end to end on float64 clients (flat
@@ -21,6 +21,8 @@ import os
 import sys
 
 import numpy as np
+
+from npz_parts import save_parts
 
 sys.dont_write_bytecode = True
 REF = "/root/reference"
@@ -126,7 +128,7 @@ def main():
     run_agg("agg|f64w32|full|flat", g64, {"compression_function": "full"}, flat,
             weights=w64.astype(np.float32), seed=15)
 
-    np.savez_compressed(os.path.join(OUT, "golden_f64.npz"), **arrays)
+    save_parts(OUT, "golden_f64", arrays)           # golden_f64.NN.npz, each below 1 MiB
     with open(os.path.join(OUT, "manifest_f64.json"), "w") as fh:
         json.dump(manifest, fh, indent=1, sort_keys=True)
     print(f"wrote {len(manifest['cases'])} float64 cases")

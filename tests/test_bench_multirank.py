@@ -82,11 +82,11 @@ def test_rccl_world1_bench_issues_its_reduce(tmp_path):
     one async reduce (the work handle waited on two steps later, stream-ordered against the
     next encodes).  The aggregate equals the world-1 fold bit for bit (a one-rank sum-reduce
     adds nothing) = the oracle's FedAVG of the rank's clients."""
-    agg = tmp_path / "agg.npy"
+    agg, outs = tmp_path / "agg.npy", tmp_path / "outputs"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--backend", "nccl",
            "--force-pg", "--clients", str(M), "--n", str(N), "--steps", "4", "--warmup", "1",
            "--no-cpu-baseline", "--no-single", "--no-matrix", "--roofline-steps", "0",
-           "--dump-agg", str(agg)]
+           "--dump-agg", str(agg), "--dump-outputs", str(outs)]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for v in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(v, None)
@@ -107,6 +107,20 @@ def test_rccl_world1_bench_issues_its_reduce(tmp_path):
         rows.append(po.decode_dense(N, idx, val))
     want = go.sequential_weighted_sum(rows, np.full(M, 1.0 / M, np.float32))
     assert got.tobytes() == want.tobytes()
+    # --dump-outputs: the same step's outputs (N is below the sample size, so nothing is left
+    # out); a run without --full times the 4 steps and does nothing else
+    assert line["steps"] == 4 and line["ms_per_step"] > 0
+    assert line["cpu_baseline"] is None and line["extra"]["self_check"] is None
+    assert not {"single_gradient", "configs_1_2", "codec_matrix"} & set(line["extra"])
+    dumped = {f[:-4]: np.load(outs / f) for f in sorted(os.listdir(outs))}
+    assert sorted(dumped) == ["aggregate", "client_first_decoded", "client_last_decoded",
+                              "sample_index"]
+    assert dumped["sample_index"].dtype == np.float64
+    assert np.array_equal(dumped["sample_index"], np.arange(N))
+    for name, ref in (("aggregate", want), ("client_first_decoded", rows[0]),
+                      ("client_last_decoded", rows[-1])):
+        assert dumped[name].dtype == np.float32
+        assert dumped[name].tobytes() == np.asarray(ref, np.float32).tobytes(), name
 
 
 @pytest.mark.gpu

@@ -14,7 +14,7 @@ import sys
 import numpy as np
 import pytest
 
-from conftest import GOLDEN_DIR, ROOT
+from conftest import GOLDEN_DIR, ROOT, load_parts
 from oracle import compression_oracle as co
 from oracle import gar_oracle as go
 
@@ -23,7 +23,7 @@ class F64Golden:
     def __init__(self):
         with open(os.path.join(GOLDEN_DIR, "manifest_f64.json")) as fh:
             self.manifest = json.load(fh)
-        self.arrays = np.load(os.path.join(GOLDEN_DIR, "golden_f64.npz"))
+        self.arrays = load_parts(GOLDEN_DIR, "golden_f64")
 
     def cases(self, prefix=""):
         return sorted(k for k in self.manifest["cases"] if k.startswith(prefix))

@@ -19,7 +19,7 @@ timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smok
 fi
 if [ -z "$SKIP_BENCH" ]; then
 echo "[r06] bench"
-timeout -k 10 400 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 400 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 cat $OUT/bench.json
 fi
 if [ -z "$SKIP_PROF" ]; then
