@@ -370,6 +370,48 @@ int fc_mt_binomial(const void* plan, size_t plan_bytes, uint64_t n, int rows, in
 int fc_mt_jump_poly(uint64_t d, uint32_t* out_words);
 int fc_mt_charpoly(uint32_t* out_words);
 
+/* ---- np.random.permutation(n)[:k] on the device: the reference's own 'rand' draws ------------
+ * Replaces np.random.permutation(n)[:k] of compression.py:43 on the process-global legacy
+ * RandomState (NumPy's shuffle of arange(n): for i = n-1 .. 1, j = random_interval(i) by masked
+ * rejection of 32-bit MT19937 outputs, swap x[i], x[j]).  idx_out equals the host call's result,
+ * order included; mask_bits equals bitmask_words(idx, n, False); the state block holds the state
+ * np.random would be left in and is updated in place, so consecutive calls chain without the
+ * host (openmsftl_amd/csrc/fc_perm.hip; pinned against NumPy in tests/test_perm_gpu.py).
+ *   fc_mt_perm_plan: the segment jump polynomials for length n (host, cached; independent of n
+ *     but for their count) into the DEVICE buffer `plan` (fc_mt_perm_plan_bytes(n));
+ *     synchronises `stream`.
+ *   fc_mt_perm_begin: (key: HOST uint32[624], pos in [0, 624]) into the DEVICE state block, its
+ *     other words zeroed.
+ *   fc_mt_permutation: one call of np.random.permutation(n)[:k] from the state block, on
+ *     `stream`, no host synchronisation.  idx_out: DEVICE uint32[k] or NULL; mask_bits: DEVICE
+ *     uint32[ceil(n/32)] (bits >= n zero) or NULL; not both NULL.  ws: DEVICE, 256-B aligned,
+ *     fc_mt_perm_workspace_bytes(n).  max_words: the most outputs the call may consume (0, or
+ *     anything above it: 2n + 4096; the expected need is ~1.4 n).  n <= 1 draws nothing.
+ *     Fallback: if the draw needs more than max_words outputs (fallback = 1) or a trace runs
+ *     into its loop bound (2), key and pos stay as they were, the outputs are unspecified and
+ *     every later call on the block draws nothing: the caller makes the host call instead.
+ *     k > n, n >= 2^31, a NULL plan / state / ws or two NULL outputs: FC_ERR_ARG; a short plan
+ *     or workspace: FC_ERR_WORKSPACE (all checked before the GPU is touched).
+ *   fc_mt_perm_timing (measurement, not thread-safe): on != 0 brackets the five stages of the
+ *     following fc_mt_permutation calls (words, parse, link, trace, commit) with HIP events;
+ *     stage_ms != NULL first waits for the last timed call and returns its five times. */
+typedef struct {
+  uint32_t key[624];              /* np.random.get_state()[1] after the calls so far */
+  uint32_t pos;                   /* ... [2] */
+  uint32_t fallback;              /* 0 ok, 1 word budget, 2 trace bound (sticky) */
+  uint32_t rows_done;             /* calls that completed */
+  uint32_t reserved;
+  uint64_t consumed;              /* MT19937 outputs consumed, summed over those calls */
+} fc_perm_state;
+size_t fc_mt_perm_plan_bytes(uint64_t n);
+int fc_mt_perm_plan(uint64_t n, void* plan, size_t plan_bytes, fc_stream_t stream);
+size_t fc_mt_perm_workspace_bytes(uint64_t n);
+int fc_mt_perm_begin(const uint32_t* key, uint32_t pos, void* state, fc_stream_t stream);
+int fc_mt_permutation(const void* plan, size_t plan_bytes, uint64_t n, uint64_t k, uint64_t max_words,
+                      void* state, uint32_t* idx_out, uint32_t* mask_bits, void* ws, size_t ws_bytes,
+                      fc_stream_t stream);
+int fc_mt_perm_timing(int on, double* stage_ms);
+
 /* Ordering of in-kernel-waiting launches issued outside the library's own calls (a replayed
  * graph that contains fc_topk_encode / fc_topk_encode_dense / fc_topk_dense_f64_sampled):
  * fc_fused_order_begin(s) makes s wait for the device's last such launch; fc_fused_order_end(s)

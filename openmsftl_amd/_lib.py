@@ -58,6 +58,14 @@ class EncodeJob(ctypes.Structure):
                 ("qoff", ctypes.c_void_p)]
 
 
+class PermState(ctypes.Structure):
+    """fc_perm_state: the device state block of fc_mt_permutation."""
+    _fields_ = [("key", ctypes.c_uint32 * 624), ("pos", ctypes.c_uint32),
+                ("fallback", ctypes.c_uint32), ("rows_done", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("consumed", ctypes.c_uint64)]
+
+
+assert ctypes.sizeof(PermState) == 2520
 assert ctypes.sizeof(PacketHdr) == HDR_BYTES
 assert ctypes.sizeof(EncodeJob) == 64
 assert ctypes.sizeof(PacketView) == 56
@@ -111,6 +119,12 @@ SIGNATURES = {
     "fc_mt_binomial": (_i32, [_vp, _sz, _u64, _i32, _i32, _dbl, _vp, _vp, _sz, _vp]),
     "fc_mt_jump_poly": (_i32, [_u64, _vp]),
     "fc_mt_charpoly": (_i32, [_vp]),
+    "fc_mt_perm_plan_bytes": (_sz, [_u64]),
+    "fc_mt_perm_plan": (_i32, [_u64, _vp, _sz, _vp]),
+    "fc_mt_perm_workspace_bytes": (_sz, [_u64]),
+    "fc_mt_perm_begin": (_i32, [_vp, ctypes.c_uint32, _vp, _vp]),
+    "fc_mt_permutation": (_i32, [_vp, _sz, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "fc_mt_perm_timing": (_i32, [_i32, ctypes.POINTER(ctypes.c_double)]),
     "fc_fused_order_begin": (_i32, [_vp]),
     "fc_fused_order_end": (_i32, [_vp]),
     "fc_timing_begin": (_i32, [ctypes.c_uint32]),

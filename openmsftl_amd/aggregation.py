@@ -178,7 +178,30 @@ def _device_mt_ok(clients) -> bool:
     return True
 
 
-def row_plan(clients, n: int, device_mt: Optional[bool] = None) -> Optional[RowPlan]:
+#: draw the reference's np.random.permutation rows on the device (openmsftl_amd/csrc/fc_perm.hip)
+#: instead of on the host producer thread.  Opt-in: the default of
+#: aggregation_config["device_permutation"] and of :func:`row_plan`'s ``device_perm``
+DEVICE_PERM = False
+
+
+def _device_perm_ok(clients, n: int) -> bool:
+    """Can the round's np.random draws be permutations made on the device?  Only if every
+    host-RNG row is a 'rand' row (a numpy dropout row in the same round keeps today's host
+    plan: the two kinds of draw share one stream) and there is something to draw."""
+    rand_rows = 0
+    for c in clients:
+        C = c.C
+        fn = C.compression_function
+        if getattr(C, "rng", "numpy") != "numpy":
+            continue
+        if fn in ("dropout-biased", "dropout-unbiased"):
+            return False
+        rand_rows += fn == "rand"
+    return rand_rows > 0 and 2 <= n < 2 ** 31
+
+
+def row_plan(clients, n: int, device_mt: Optional[bool] = None,
+             device_perm: Optional[bool] = None) -> Optional[RowPlan]:
     """The streamed round's :class:`~openmsftl_amd.pipeline.RowPlan` (aggregation.py:61-63:
     row ix = compress(clients[ix].grad)), or None when some client's codec cannot stream.
 
@@ -193,11 +216,15 @@ def row_plan(clients, n: int, device_mt: Optional[bool] = None) -> Optional[RowP
     consumption of the global RNG; Philox offsets are taken in row order too.  With
     ``device_mt`` (default :data:`DEVICE_MT`) and no host permutation in the round, the dropout
     masks are np.random's own draws made on the device instead (mask_src "mt": row r of the
-    round's MtRound, from np.random's state now; :meth:`RowPlan.close` sets the state after)."""
+    round's MtRound, from np.random's state now; :meth:`RowPlan.close` sets the state after).
+    With ``device_perm`` (default :data:`DEVICE_PERM`, off) and no numpy dropout row in the
+    round, its 'rand' rows are np.random.permutation's own draws made on the device (mask_src
+    "perm": draw ``offset`` of the round's PermRound, in row order on one device)."""
     if not all(_streamable(c.C, n) for c in clients):
         return None
     use_mt = (DEVICE_MT if device_mt is None else device_mt) and _device_mt_ok(clients)
-    mt_rows = 0
+    use_perm = (DEVICE_PERM if device_perm is None else device_perm) and _device_perm_ok(clients, n)
+    mt_rows = perm_rows = 0
     specs, draws = [], {}
     for i, c in enumerate(clients):
         C = c.C
@@ -208,6 +235,11 @@ def row_plan(clients, n: int, device_mt: Optional[bool] = None) -> Optional[RowP
         rng = getattr(C, "rng", "numpy")
         if fn in ("top", "rand"):
             k = kept_count(C.fraction_coordinates, n)
+            if fn == "rand" and rng == "numpy" and use_perm:
+                specs.append(RowCodec("mask", codec=L.FC_CODEC_RAND, mask_src="perm", k=k,
+                                      offset=perm_rows))
+                perm_rows += 1
+                continue
             if fn == "rand" and rng == "numpy":
                 specs.append(RowCodec("mask", codec=L.FC_CODEC_RAND, mask_src="host"))
                 draws[i] = (lambda k=k: bitmask_words(np.random.permutation(n)[:k], n, False))
@@ -233,7 +265,7 @@ def row_plan(clients, n: int, device_mt: Optional[bool] = None) -> Optional[RowP
         else:
             specs.append(RowCodec("mask", codec=cid, p=p, mask_src="philox", seed=C.seed,
                                   offset=C._next_offset()))
-    return RowPlan(n, specs, draws, mt_rows=mt_rows)
+    return RowPlan(n, specs, draws, mt_rows=mt_rows, perm_rows=perm_rows)
 
 
 #: device bytes the streamed path may hold (gradient ring + packets + aggregates);
@@ -378,7 +410,10 @@ def aggregate_grads(self, clients: List, input_feature: np.ndarray = None,
     all_f32 = all(np.asarray(c.grad).dtype == np.float32 for c in clients)
     streamable = device_gar and all_f32 and f32_weights and n > 0
     if streamable:
-        plan = row_plan(clients, n)
+        # device permutations chain through one device state block: one device only
+        cfg = getattr(self, "aggregation_config", None) or {}
+        want_perm = bool(cfg.get("device_permutation", DEVICE_PERM))
+        plan = row_plan(clients, n, device_perm=want_perm and len(stream_devices(self)) == 1)
     if plan is not None:
         # streamed from the host gradients, G never built (rows live group by group)
         self.agg_path = "stream"
@@ -398,11 +433,13 @@ def aggregate_grads(self, clients: List, input_feature: np.ndarray = None,
                 raise
             try:
                 plan.close()                # every draw done: the RNG is where the reference leaves it
-            except MtRedraw:                # NumPy would redraw somewhere (~2^-52 per element):
-                plan = row_plan(clients, n, device_mt=False)   # the reference's host draws
+            except MtRedraw:                # NumPy would redraw somewhere (~2^-52 per element),
+                # or a device permutation fell back: the reference's host draws
+                plan = row_plan(clients, n, device_mt=False, device_perm=False)
                 continue
             break
-        self.agg_draws = "device-mt" if plan.mt_rows else ("host" if plan.draws else None)
+        self.agg_draws = ("device-mt" if plan.mt_rows else "device-perm" if plan.perm_rows
+                          else "host" if plan.draws else None)
     else:
         # generic codec mix / float64: the drop-in Compression per client, in row order; rows
         # take G's dtype (aggregation.py:61-63: G = zeros(..., dtype=clients[0].grad.dtype))
@@ -451,7 +488,7 @@ class Aggregator:
         self.curr_G = None
         self.agg_grad = None
         self.agg_path = None                # "stream" | "dense-fold" | "dense": the last call's path
-        self.agg_draws = None               # streamed np.random draws: "device-mt" | "host" | None
+        self.agg_draws = None               # streamed np.random draws: "device-mt" | "device-perm" | "host" | None
         self.analyze_pc = self.aggregation_config.get("pc_analysis", False)
         self.num_hierarchies = self.aggregation_config.get("num_hierarchies", 0)
         self.cluster_size_list = self.aggregation_config.get("cluster_size_list", [])

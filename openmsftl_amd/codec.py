@@ -973,3 +973,127 @@ def mt_state():
 def mt_set_state(key: np.ndarray, pos: int, has_gauss: int, gauss: float) -> None:
     np.random.set_state(("MT19937", np.asarray(key, dtype=np.uint32), int(pos), int(has_gauss),
                          float(gauss)))
+
+
+# ---- np.random.permutation on the device (the reference's 'rand' draws) ------------------------
+class PermPlan:
+    """The segment jump polynomials of length n on one device (fc_mt_perm_plan), kept per
+    (device, n)."""
+
+    _cache: dict = {}
+    _lock = threading.Lock()
+
+    def __init__(self, n: int, device: torch.device):
+        lib = L.load()
+        self.n = n
+        self.nbytes = int(lib.fc_mt_perm_plan_bytes(n))
+        if self.nbytes == 0:
+            raise ValueError(f"n={n} outside [0, 2^31)")
+        self.ws_bytes = int(lib.fc_mt_perm_workspace_bytes(n))
+        self.buf = torch.empty(self.nbytes, dtype=torch.uint8, device=device)
+        with torch.cuda.device(device):
+            L.check(lib.fc_mt_perm_plan(n, _vp(self.buf), self.nbytes, _stream(device)),
+                    "fc_mt_perm_plan")
+
+    @classmethod
+    def get(cls, n: int, device: torch.device) -> "PermPlan":
+        key = (device.index if device.index is not None else torch.cuda.current_device(), n)
+        with cls._lock:
+            p = cls._cache.get(key)
+            if p is None:
+                p = cls._cache[key] = cls(n, device)
+            return p
+
+
+class PermRound:
+    """Consecutive ``np.random.permutation(n)[:k]`` draws (compression.py:43) made on the device
+    from the legacy state (key, pos) of ``np.random.get_state()`` (fc_mt_perm_begin /
+    fc_mt_permutation).  The state lives in a device block that every call updates in place:
+    calls chain in the order they are made, with no host read between them.  :meth:`end_state`
+    gives the state np.random is left in and the fallback word (non-zero: a call ran out of its
+    word budget or a loop bound; key and pos are then those before that call, the calls from it
+    on drew nothing and the caller draws on the host instead)."""
+
+    STATE_BYTES = 2520
+    #: the word budget of a call made with ``max_words=0`` (0: the library's 2n + 4096)
+    max_words = 0
+
+    def __init__(self, n: int, key: np.ndarray, pos: int, device: Optional[torch.device] = None):
+        dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
+        lib = L.load()
+        self.n, self.dev = int(n), dev
+        self.plan = PermPlan.get(self.n, dev)
+        self.nbytes = self.plan.ws_bytes
+        self.ws = torch.empty(self.nbytes, dtype=torch.uint8, device=dev)
+        self.state = torch.empty(self.STATE_BYTES, dtype=torch.uint8, device=dev)
+        self._key = np.ascontiguousarray(np.asarray(key, dtype=np.uint32))
+        if self._key.shape != (624,):
+            raise ValueError("an MT19937 key has 624 words")
+        self._lock = threading.Lock()
+        self._home = torch.cuda.current_stream(dev)      # the stream the buffers belong to
+        with torch.cuda.device(dev):
+            L.check(lib.fc_mt_perm_begin(self._key.ctypes.data_as(ctypes.c_void_p), int(pos),
+                                         _vp(self.state), _stream(dev)), "fc_mt_perm_begin")
+        self._last = (self._event(self._home), self._home)
+
+    def _event(self, stream) -> torch.cuda.Event:
+        ev = torch.cuda.Event()
+        ev.record(stream)
+        return ev
+
+    def permutation(self, k: int, out_idx: Optional[torch.Tensor] = None,
+                    out_mask: Optional[torch.Tensor] = None, max_words: int = 0):
+        """The next ``np.random.permutation(n)[:k]`` on the current stream -> (idx, mask):
+        ``idx`` int32[k] (the uint32 indices, in NumPy's order) and ``mask`` int32 bit words
+        (ceil(n/32), = ``bitmask_words(idx, n, False)``).  With only one of ``out_idx`` /
+        ``out_mask`` given only that output is made (the other is None); with neither, both
+        are allocated."""
+        n, k = self.n, int(k)
+        if not 0 <= k <= n:
+            raise ValueError(f"k={k} outside [0, n={n}]")
+        if out_idx is None and out_mask is None:
+            out_idx = torch.empty(k, dtype=torch.int32, device=self.dev)
+            out_mask = torch.empty((n + 31) // 32, dtype=torch.int32, device=self.dev)
+        for t, size, name in ((out_idx, k, "out_idx"), (out_mask, (n + 31) // 32, "out_mask")):
+            if t is not None and (t.dtype != _U32 or not t.is_cuda or not t.is_contiguous()
+                                  or t.numel() < size):
+                raise ValueError(f"{name} must be a contiguous int32 CUDA tensor of {size} words")
+        if n == 0:
+            return out_idx, out_mask
+        if out_mask is None and k == 0:                  # nothing to write, the draw still runs
+            out_mask = torch.empty((n + 31) // 32, dtype=torch.int32, device=self.dev)
+        lib = L.load()
+        cur = torch.cuda.current_stream(self.dev)
+        with self._lock:
+            ev, last = self._last
+            if cur != last:                              # the state chains across streams
+                cur.wait_event(ev)
+            if cur != self._home:
+                for t in (self.ws, self.state, self.plan.buf):
+                    t.record_stream(cur)
+            with torch.cuda.device(self.dev):
+                L.check(lib.fc_mt_permutation(_vp(self.plan.buf), self.plan.nbytes, n, k,
+                                              int(max_words or self.max_words), _vp(self.state),
+                                              _vp(out_idx if k else None), _vp(out_mask),
+                                              _vp(self.ws), self.nbytes, _stream(self.dev)),
+                        "fc_mt_permutation")
+            self._last = (self._event(cur), cur)
+        return out_idx, out_mask
+
+    def end_state(self):
+        """(key uint32[624], pos, fallback, consumed) after the calls made so far
+        (synchronises with the last of them)."""
+        with self._lock:
+            ev = self._last[0]
+        ev.synchronize()
+        raw = self.state.cpu().numpy()
+        words = raw[:2512].view(np.uint32)
+        return (words[:624].copy(), int(words[624]), int(words[625]),
+                int(raw[2512:2520].view(np.uint64)[0]))
+
+    def rows_done(self) -> int:
+        """Calls that completed (synchronises)."""
+        with self._lock:
+            ev = self._last[0]
+        ev.synchronize()
+        return int(self.state[2504:2508].cpu().numpy().view(np.uint32)[0])

@@ -11,7 +11,9 @@ The compute runs in hand-written HIP kernels (libfedcodec.so); there is no CPU f
 
 RNG: by default ('rng': 'numpy') 'rand'/'dropout-*' draw from the process-global legacy
 ``np.random`` exactly as the reference (same stream consumption, same state afterwards):
-'rand' calls ``np.random.permutation`` and only the index set crosses to the GPU; 'dropout-*'
+'rand' calls ``np.random.permutation`` and only the index set crosses to the GPU (or, with the
+opt-in key ``'device_permutation': True``, makes that very draw on the device:
+openmsftl_amd/csrc/fc_perm.hip, same indices, same state afterwards); 'dropout-*'
 generates ``np.random.binomial``'s own MT19937 variates on the device (jump-ahead from
 ``np.random.get_state()``, openmsftl_amd/csrc/fc_mt.hip) and sets the state after them.  ``'rng': 'philox'`` draws on the device instead
 (Philox4x32-10 keyed by ``'seed'``, counter advanced per call) — no host RNG work, not
@@ -43,6 +45,11 @@ from . import codec
 #: 'dropout-*' with the numpy RNG: draw np.random.binomial's MT19937 variates on the device
 #: (bit-exact, RNG state included; openmsftl_amd/csrc/fc_mt.hip) instead of calling it
 DEVICE_MT = True
+
+#: 'rand' with the numpy RNG: draw np.random.permutation(n)[:k] on the device (bit-exact, order
+#: and RNG state included; openmsftl_amd/csrc/fc_perm.hip) instead of calling it.  Opt-in: the
+#: default of the config key "device_permutation"
+DEVICE_PERM = False
 
 
 def _valid_p(p) -> bool:
@@ -85,6 +92,7 @@ class Compression:
         # opts into this build's QSGD (the reference's commented formula, :65-74; num_bits as
         # the reference reads it; Philox keyed by 'seed'; parity unpinned: DESIGN.md §6)
         self.qsgd = compression_config.get("qsgd", None)
+        self.device_permutation = bool(compression_config.get("device_permutation", DEVICE_PERM))
         self._calls = 0
 
     # ------------------------------------------------------------------------------------
@@ -105,6 +113,12 @@ class Compression:
             k = kept_count(self.fraction_coordinates, n)
             host_idx = None
             if fn == 'rand' and self.rng == 'numpy':
+                if self.device_permutation and n >= 2:
+                    out = self._rand_device(grad, n, k, on_device)
+                    if out is not None:
+                        return out
+                    # the device call fell back (its word budget or a loop bound): NumPy's own
+                    # call below, from the same (untouched) state
                 host_idx = np.random.permutation(n)[:k]          # compression.py:43
             if n == 0:
                 return grad.clone() if on_device else np.zeros_like(grad)
@@ -176,6 +190,29 @@ class Compression:
             return grad.clone() if on_device else np.zeros_like(grad)
         pkt = codec.encode_qsgd(g, int(self.num_bits), seed=self.seed, offset=self._next_offset())
         out = codec.decode_qsgd(pkt)
+        return out if on_device else out.cpu().numpy()
+
+    def _rand_device(self, grad, n: int, k: int, on_device: bool):
+        """'rand' with np.random.permutation(n)[:k] drawn on the device from np.random's state
+        (fc_perm.hip), np.random left where the call leaves it; None when the device call fell
+        back or the gradient is one the host path rejects (after its draw)."""
+        try:
+            g = self._to_device(grad)
+        except (TypeError, ValueError):
+            return None
+        key, pos, has_gauss, gauss = codec.mt_state()
+        R = codec.PermRound(n, key, pos, g.device)
+        _, mask = R.permutation(k, out_mask=torch.empty((n + 31) // 32, dtype=torch.int32,
+                                                        device=g.device))
+        if g.dtype == torch.float64:
+            out = codec.mask_dense_f64(g, L.FC_CODEC_RAND, mask_bits=mask)
+        else:
+            out = codec.decode(codec.encode_mask(g, L.FC_CODEC_RAND, mask_bits=mask,
+                                                 fmt=L.FC_FMT_IDXVAL))
+        key, pos, fallback, _ = R.end_state()
+        if fallback:
+            return None
+        codec.mt_set_state(key, pos, has_gauss, gauss)
         return out if on_device else out.cpu().numpy()
 
     def _next_offset(self) -> int:

@@ -7,3 +7,4 @@
 #include "fc_f64.hip"
 #include "fc_capi.hip"
 #include "fc_mt.hip"
+#include "fc_perm.hip"

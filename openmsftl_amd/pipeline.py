@@ -95,9 +95,10 @@ class RowCodec:
     PHILOX = native 'rand' keyed by ``seed``/``offset``); "mask": fc_mask_encode idx/val packet
     of codec ``codec`` (FC_CODEC_RAND / DROPOUT_*) with ``mask_src`` "host" (bits drawn on the
     host, :meth:`RowPlan.take_mask`), "mt" (np.random.binomial's own MT19937 draws made on the
-    device, row ``offset`` of the plan's :class:`~openmsftl_amd.codec.MtRound`), "philox"
-    (device Bernoulli(p)) or "none" (nothing kept: 'top' with k = 0); "dense": the gradient
-    itself ('full', or 'top' with k = n)."""
+    device, row ``offset`` of the plan's :class:`~openmsftl_amd.codec.MtRound`), "perm"
+    (np.random.permutation(n)[:k] made on the device, draw number ``offset`` of the plan's
+    :class:`~openmsftl_amd.codec.PermRound`), "philox" (device Bernoulli(p)) or "none" (nothing
+    kept: 'top' with k = 0); "dense": the gradient itself ('full', or 'top' with k = n)."""
     kind: str
     k: int = 0
     key_mode: int = 0
@@ -110,8 +111,9 @@ class RowCodec:
 
 class MtRedraw(RuntimeError):
     """NumPy's binomial would have redrawn a variate (probability ~2^-52 per element) in a
-    device MT19937 round: its masks from that element on are not the reference's; redo the
-    round with host draws (np.random is still at the round's start)."""
+    device MT19937 round, or a device permutation fell back (its word budget or a loop bound):
+    the round's masks from there on are not the reference's; redo the round with host draws
+    (np.random is still at the round's start)."""
 
 
 class RowPlan:
@@ -134,11 +136,17 @@ class RowPlan:
 
     def __init__(self, n: int, specs: Sequence[RowCodec], draws: Optional[dict] = None,
                  lookahead: int = 8, base: int = 0, parent: "RowPlan" = None,
-                 mt_rows: int = 0):
+                 mt_rows: int = 0, perm_rows: int = 0):
         self.n, self.specs, self.base = n, specs, base
         self._root = parent if parent is not None else self
         if parent is not None:
             return
+        # device permutation rows ("perm"): drawn in row order from one PermRound that starts
+        # at np.random's state now; close() sets np.random from its end state
+        self.perm_rows = perm_rows
+        self._perm_start = codec.mt_state() if perm_rows else None
+        self._perm_round = None
+        self._perm_drawn = 0
         # device MT19937 rows ("mt"): the round's start state is np.random's now; close() leaves
         # np.random where the reference's loop would (the state after mt_rows binomial draws)
         self.mt_rows = mt_rows
@@ -267,6 +275,36 @@ class RowPlan:
             raise r._err[1]
         if wait and r.mt_rows:
             r._mt_finish()
+        if wait and r.perm_rows:
+            r._perm_finish()
+
+    # ---- device permutation rows -----------------------------------------------------------
+    def perm_mask(self, dev: torch.device, rc: RowCodec, out: torch.Tensor) -> torch.Tensor:
+        """The mask words of the round's next 'rand' row, drawn on ``dev``'s current stream
+        from the plan's :class:`~openmsftl_amd.codec.PermRound` (begun there the first time).
+        The rows chain through one device state block, so they are drawn in row order."""
+        r = self._root
+        with r._mt_lock:
+            if rc.offset != r._perm_drawn:
+                raise RuntimeError(f"device permutation rows are drawn in row order (draw "
+                                   f"{rc.offset} asked after {r._perm_drawn})")
+            if r._perm_round is None:
+                k, pos, _, _ = r._perm_start
+                r._perm_round = codec.PermRound(r.n, k, pos, dev)
+            elif r._perm_round.dev != dev:
+                raise RuntimeError("device permutation rows run on one device")
+            r._perm_drawn += 1
+            return r._perm_round.permutation(rc.k, out_mask=out)[1]
+
+    def _perm_finish(self) -> None:
+        if self._perm_round is None or self._perm_drawn != self.perm_rows:
+            raise RuntimeError(f"{self._perm_drawn} of {self.perm_rows} device permutation rows "
+                               "were drawn")
+        key, pos, fallback, _ = self._perm_round.end_state()     # synchronises
+        if fallback:
+            raise MtRedraw(f"a device permutation fell back (code {fallback})")
+        _, _, has_gauss, gauss = self._perm_start
+        codec.mt_set_state(key, pos, has_gauss, gauss)
 
     # ---- device MT19937 rows --------------------------------------------------------------
     def mt_round(self, dev: torch.device) -> "codec.MtRound":
@@ -526,6 +564,8 @@ class HostFedAvg:
                 # made while the row's gradient is still on its way (the slot's previous
                 # encode, its last reader, is earlier on this stream)
                 mask = plan.mt_round(self.dev).binomial(rc.offset, rc.p, out=self._mslot(s))
+            elif rc.mask_src == "perm":             # np.random.permutation's draws, likewise
+                mask = plan.perm_mask(self.dev, rc, self._mslot(s))
             comp.wait_event(self.h2d_done[s])
             if rc.kind == "top":
                 codec.encode_top(self.slots[s], rc.k, key_mode=rc.key_mode, seed=rc.seed,
@@ -667,6 +707,9 @@ def _ring_worker(pipe: HostFedAvg, get, w: np.ndarray, groups: List[range], mine
     already holds it or t == 0 — and ``give(t, acc, event)`` hands the result on."""
     if pipe.sets < 2:
         raise ValueError("ring pipelines need sets=2 (one set encodes, one waits)")
+    if plan._root.perm_rows:
+        raise ValueError("device permutation rows need one device and one rank: plan the "
+                         "round with device_perm=False")
     done = [None] * pipe.sets
     with torch.cuda.device(pipe.dev), torch.cuda.stream(comp):
         pipe.begin()
