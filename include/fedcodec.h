@@ -172,6 +172,32 @@ int fc_topk_encode_decode(const float* g, uint64_t n, uint64_t k, uint16_t* idx,
 int fc_topk_encode_dense(const float* g, uint64_t n, uint64_t k, uint16_t* idx, float* val,
                          uint64_t capacity, uint32_t* cnt, uint64_t* qoff, fc_packet_hdr* hdr,
                          void* ws, size_t ws_bytes, float* dense, fc_stream_t stream);
+/* ---- top-k with error feedback (residual accumulation; opt-in, no reference counterpart) --
+ * compression.py:31-37 drops the N - k unselected coordinates for good; with error feedback
+ * the client adds them to its next gradient.  One streaming pass over g and the residual:
+ *   a  = fl32(g + res_in)                       one IEEE fp32 add per element
+ *   packet                                      exactly what fc_topk_encode(a, ...) writes (keys
+ *                                               on |a|, highest index first in a tie, NaN largest,
+ *                                               val = a[idx], cnt, qoff, header: codec TOP, format
+ *                                               IDXVAL, T64, L64): decoders take it unchanged
+ *   res_out[i] = +0.0f at the k selected coordinates (also for a selected NaN or +-inf, where
+ *                a - q would be NaN), a[i] everywhere else (an unselected -0.0 stays -0.0)
+ * g and res_in are never written; res_out (float32[n]) must not overlap either.  All three are
+ * 16-B aligned.  Needs 0 < k < n.  Launches: sample, compaction, resolve — the unfused chain,
+ * no kernel that waits in-kernel for another workgroup, so no fc_fused_order_* handling.
+ * Header status FC_STATUS_RETRY_EXACT: the packet AND res_out are not valid; run the fallback
+ *   fc_ef_sum(g, res_in, res_out) -> fc_topk_encode_exact(res_out, ...) -> fc_ef_clear(pkt, res_out)
+ * which is also the form for k == 0 (empty packet, res_out = a) and k == n (res_out all +0).
+ * fc_ef_sum:   res_out = fl32(g + res_in)  (same aliasing and alignment rules).
+ * fc_ef_clear: +0.0f into res_out at every entry of the idx/val packet the decoders keep
+ *   (composite >= T64); pkt: HOST pointer to one view (its hdr, cnt, idx, val on the device).
+ * Argument errors (NULL, alignment, aliasing, k, capacity: FC_ERR_ARG; a short workspace:
+ * FC_ERR_WORKSPACE) are reported before the GPU is touched. */
+int fc_topk_encode_ef(const float* g, const float* res_in, float* res_out, uint64_t n, uint64_t k,
+                      uint16_t* idx, float* val, uint64_t capacity, uint32_t* cnt, uint64_t* qoff,
+                      fc_packet_hdr* hdr, void* ws, size_t ws_bytes, fc_stream_t stream);
+int fc_ef_sum(const float* g, const float* res_in, float* res_out, uint64_t n, fc_stream_t stream);
+int fc_ef_clear(const fc_packet_view* pkt, uint64_t n, float* res_out, fc_stream_t stream);
 /* ---- batched top-k / native rand-k: M clients, one launch per pipeline stage ----------
  * The same fast path as fc_topk_encode for m gradients of equal length n, with the grid's
  * y dimension indexing the client: 4 launches for the whole batch instead of 4 per client,

@@ -87,6 +87,10 @@ SIGNATURES = {
                                     _vp, _vp]),
     "fc_topk_encode_decode": (_i32, [_vp, _u64, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _sz,
                                      _vp, _vp]),
+    "fc_topk_encode_ef": (_i32, [_vp, _vp, _vp, _u64, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp,
+                                 _sz, _vp]),
+    "fc_ef_sum": (_i32, [_vp, _vp, _vp, _u64, _vp]),
+    "fc_ef_clear": (_i32, [ctypes.POINTER(PacketView), _u64, _vp, _vp]),
     "fc_workspace_bytes_batch": (_sz, [_u64, _i32]),
     "fc_topk_encode_batch": (_i32, [_vp, _i32, _u64, _u64, _i32, _u64, _vp, _sz, _vp]),
     "fc_topk_encode_batch_part": (_i32, [_vp, _i32, _u64, _u64, _i32, _u64, _vp, _sz, _i32, _vp]),

@@ -119,6 +119,8 @@ def common_top_fraction(clients) -> Optional[float]:
         C = c.C
         if getattr(C, "compression_function", None) != "top":
             return None
+        if getattr(C, "error_feedback", False):      # stateful: only compress() may run it
+            return None
         f = C.fraction_coordinates
         if fr is None:
             fr = f
@@ -140,6 +142,10 @@ def _streamable(C, n: int) -> bool:
         return False
     if fn == "full":
         return True
+    if getattr(C, "error_feedback", False):
+        # a codec with state (the 'top' residual): the streamed paths re-run rows (MtRedraw) and
+        # must never see it; the generic path calls compress() exactly once per row, in row order
+        return False
     rng = getattr(C, "rng", "numpy")           # a reference Compression draws from np.random
     if rng not in ("numpy", "philox"):
         return False

@@ -1,6 +1,7 @@
 """Device-resident codec API over libfedcodec.so (torch tensors in HBM, torch's stream).
 
     pkt = encode_top(g, k)                 # compression.py:31-37   (one read of g)
+    pkt, e2 = encode_top_ef(g, e, k)       # top-k of g + e, e2 = what it dropped (error feedback)
     pkt = encode_rand_philox(g, k, seed)   # compression.py:39-45   native RNG
     pkt = encode_mask(g, codec, p, ...)    # compression.py:47-60 / rand parity
     q   = decode(pkt)                      # the dense vector compress() returns
@@ -84,6 +85,7 @@ class Packet:
     bitmap: Optional[torch.Tensor] = None
     k: int = 0
     qoff: Optional[torch.Tensor] = None    # int64[num_chunks]: quarter offsets (FC_FMT_IDXVAL)
+    retried: bool = False                  # encode_top_ef: the exact chain wrote this packet
 
     @classmethod
     def alloc(cls, n: int, fmt: int, device, hdr: Optional[torch.Tensor] = None,
@@ -204,6 +206,72 @@ def encode_top(g: torch.Tensor, k: int, *, key_mode: int = L.FC_KEY_MAGNITUDE, s
     if check:
         resolve([packet])
     return packet
+
+
+def _ef_exact(g: torch.Tensor, residual: torch.Tensor, residual_out: torch.Tensor, k: int,
+              packet: Packet) -> None:
+    """The exact error-feedback chain (include/fedcodec.h): fc_ef_sum, the exact encode of the
+    sum held in ``residual_out``, fc_ef_clear.  Also the form for k = 0 and k = n."""
+    lib = L.load()
+    n = g.numel()
+    s = _stream(g.device)
+    ws = Workspace.get(n, g.device)
+    L.check(lib.fc_ef_sum(_vp(g), _vp(residual), _vp(residual_out), n, s), "fc_ef_sum")
+    L.check(lib.fc_topk_encode_exact(_vp(residual_out), n, k, L.FC_KEY_MAGNITUDE, 0, 0,
+                                     _vp(packet.idx), _vp(packet.val), packet.capacity,
+                                     _vp(packet.cnt), _vp(packet.qoff), _vp(packet.hdr),
+                                     _vp(ws.buf), ws.nbytes, s), "fc_topk_encode_exact")
+    v = packet.view()
+    L.check(lib.fc_ef_clear(ctypes.byref(v), n, _vp(residual_out), s), "fc_ef_clear")
+
+
+def encode_top_ef(g: torch.Tensor, residual: Optional[torch.Tensor], k: int, *,
+                  residual_out: Optional[torch.Tensor] = None, packet: Optional[Packet] = None,
+                  check: bool = True, exact: bool = False):
+    """Top-k with error feedback (fc_topk_encode_ef): ``a = fl32(g + residual)`` is encoded
+    (the packet is exactly ``encode_top(a, k)``'s) and ``residual_out`` becomes ``+0`` at the
+    k selected coordinates and ``a`` everywhere else, in one pass over g and the residual.
+    Returns ``(packet, residual_out)``.
+
+    ``residual=None`` means zeros.  Neither ``g`` nor ``residual`` is written; ``residual_out``
+    (allocated when None) must not share memory with them.  ``check=True`` reads the status
+    and, if the sampled bracket missed, runs the exact chain itself (``packet.retried`` tells);
+    with ``check=False`` call :func:`resolve` later, until then ``residual_out`` is only valid
+    if the header says OK.  ``exact=True``, k = 0 and k = n always take the exact chain."""
+    _require_cuda_f32(g)
+    n = g.numel()
+    if not 0 <= k <= n:
+        raise ValueError(f"k={k} outside [0, {n}]")
+    if n == 0:
+        raise ValueError("empty gradient")
+    if residual is None:
+        residual = torch.zeros(n, dtype=torch.float32, device=g.device)
+    if residual_out is None:
+        residual_out = torch.empty(n, dtype=torch.float32, device=g.device)
+    for t, name in ((residual, "residual"), (residual_out, "residual_out")):
+        _require_cuda_f32(t, name)
+        if t.numel() != n or t.device != g.device:
+            raise ValueError(f"{name} must have n elements on g's device")
+    if packet is None:
+        packet = Packet.alloc(n, L.FC_FMT_IDXVAL, g.device, k=k)
+    packet.k = k
+    packet._enc = ("ef", g, residual, residual_out, k)
+    packet._dense_only = False
+    packet.retried = False
+    if exact or k == 0 or k == n:
+        _ef_exact(g, residual, residual_out, k, packet)
+        packet.retried = bool(exact)
+    else:
+        lib = L.load()
+        ws = Workspace.get(n, g.device)
+        L.check(lib.fc_topk_encode_ef(_vp(g), _vp(residual), _vp(residual_out), n, k,
+                                      _vp(packet.idx), _vp(packet.val), packet.capacity,
+                                      _vp(packet.cnt), _vp(packet.qoff), _vp(packet.hdr),
+                                      _vp(ws.buf), ws.nbytes, _stream(g.device)),
+                "fc_topk_encode_ef")
+    if check:
+        resolve([packet])
+    return packet, residual_out
 
 
 def encode_decode_top(g: torch.Tensor, k: int, *, packet: Optional[Packet] = None,
@@ -565,6 +633,15 @@ def resolve(packets: Sequence[Packet]) -> int:
             continue
         if h.status != L.FC_STATUS_RETRY_EXACT or getattr(p, "_enc", None) is None:
             raise L.FedCodecError(f"packet status {h.status}")
+        if isinstance(p._enc[0], str):                # error feedback: the exact chain on g + e
+            _, g, res, res_out, k = p._enc
+            _ef_exact(g, res, res_out, k, p)
+            redo += 1
+            p.retried = True
+            h2 = p.header()
+            if h2.status != L.FC_STATUS_OK:
+                raise L.FedCodecError(f"exact encode status {h2.status}")
+            continue
         g, k, key_mode, seed, offset = p._enc
         ws = Workspace.get(g.numel(), g.device)
         L.check(lib.fc_topk_encode_exact(_vp(g), g.numel(), k, key_mode, seed, offset,

@@ -19,6 +19,11 @@ generates ``np.random.binomial``'s own MT19937 variates on the device (jump-ahea
 (Philox4x32-10 keyed by ``'seed'``, counter advanced per call) — no host RNG work, not
 stream-identical to the reference (documented in DESIGN.md).
 
+Error feedback (opt-in key ``'error_feedback': True``, 'top' on float32 gradients only; the
+reference keeps no state between calls): the object keeps on the device what its calls so far
+dropped and adds it to the next gradient (:meth:`Compression._top_ef`, ``get_residual`` /
+``set_residual`` / ``reset_residual``).
+
 Inputs: 1-D float32 NumPy arrays (the reference's `client.grad`, client.py:53) or 1-D
 float32 CUDA tensors (device-resident; the result is then a CUDA tensor).  float64 gradients
 (what ``RandomGaussian`` with ``noise_scale == 0`` hands over, attack_models.py:105-106) run
@@ -93,6 +98,12 @@ class Compression:
         # the reference reads it; Philox keyed by 'seed'; parity unpinned: DESIGN.md §6)
         self.qsgd = compression_config.get("qsgd", None)
         self.device_permutation = bool(compression_config.get("device_permutation", DEVICE_PERM))
+        # error feedback for 'top' (opt-in; False = the reference, which keeps no state between
+        # calls): see _top_ef
+        self.error_feedback = bool(compression_config.get("error_feedback", False))
+        self._residual = None              # device float32[n]: what the calls so far dropped
+        self._residual_spare = None        # the buffer the next call writes
+        self._residual_numpy = True        # kind of the last input (get_residual's return kind)
         self._calls = 0
 
     # ------------------------------------------------------------------------------------
@@ -102,6 +113,10 @@ class Compression:
         fn = self.compression_function
         if fn == 'full':
             return grad
+        if self.error_feedback:
+            if fn != 'top':
+                raise NotImplementedError(f"error_feedback is built for 'top' only (got {fn!r})")
+            return self._top_ef(grad)
         if fn == 'qsgd' and self.qsgd == 'native':
             return self._qsgd(grad)
         if fn not in ('top', 'rand', 'dropout-biased', 'dropout-unbiased'):
@@ -181,6 +196,71 @@ class Compression:
         return out if on_device else out.cpu().numpy()
 
     # ------------------------------------------------------------------------------------
+    def _top_ef(self, grad):
+        """'top' with error feedback (config key ``"error_feedback": True``; not in the
+        reference): the coordinates this call drops are added to the next call's gradient.
+
+            a = fl32(grad + residual);  q = top-k of a (compression.py:31-37 on a);
+            residual = +0 where q took the coordinate, a everywhere else
+
+        in one device pass (codec.encode_top_ef).  Returns q as compress() returns it: a fresh
+        array of the input's dtype and kind, the input untouched.  The residual lives on the
+        device between calls: 4N bytes per Compression object (one per client, client.py:23),
+        8N while a call runs (the new residual is written beside the old one, then the two
+        buffers swap).  It advances on EVERY call: a caller that compresses one gradient twice
+        per round (DGA does, aggregation.py:188,199 of the reference) must snapshot it with
+        :meth:`get_residual` before the first call and :meth:`set_residual` it back before the
+        second.  float32 gradients only; the length may not change between calls
+        (:meth:`reset_residual` starts over)."""
+        L.load()
+        on_device = isinstance(grad, torch.Tensor)
+        g = self._to_device(grad)
+        if g.dtype != torch.float32:
+            raise NotImplementedError("error_feedback handles float32 gradients only "
+                                      f"(got {g.dtype})")
+        n = g.numel()
+        if n == 0:
+            return grad.clone() if on_device else np.zeros_like(grad)
+        if g.data_ptr() % 16:
+            g = g.clone()
+        res = self._residual
+        if res is not None and (res.numel() != n or res.device != g.device):
+            raise ValueError(f"error_feedback: gradient of {n} elements on {g.device}, residual "
+                             f"of {res.numel()} on {res.device} (reset_residual() starts over)")
+        if res is None:
+            res = torch.zeros(n, dtype=torch.float32, device=g.device)
+        spare = self._residual_spare
+        if spare is None or spare.numel() != n or spare.device != g.device:
+            spare = torch.empty(n, dtype=torch.float32, device=g.device)
+        k = kept_count(self.fraction_coordinates, n)
+        pkt, new = codec.encode_top_ef(g, res, k, residual_out=spare)
+        self._residual, self._residual_spare = new, res
+        self._residual_numpy = not on_device
+        out = codec.decode(pkt)
+        return out if on_device else out.cpu().numpy()
+
+    def get_residual(self):
+        """A copy of the error-feedback residual, of the kind of the last input (NumPy array or
+        CUDA tensor); None before the first call."""
+        if self._residual is None:
+            return None
+        return self._residual.cpu().numpy() if self._residual_numpy else self._residual.clone()
+
+    def set_residual(self, x) -> None:
+        """Replace the residual with a copy of ``x`` (1-D float32 NumPy array or tensor)."""
+        on_device = isinstance(x, torch.Tensor)
+        t = self._to_device(x)
+        if t.dtype != torch.float32:
+            raise TypeError(f"the residual is float32 (got {t.dtype})")
+        if on_device or t.data_ptr() % 16:
+            t = t.clone()
+        self._residual, self._residual_spare = t, None
+        self._residual_numpy = not on_device
+
+    def reset_residual(self) -> None:
+        """Forget the residual: the next call starts from zeros (any length)."""
+        self._residual = self._residual_spare = None
+
     def _qsgd(self, grad):
         """compression.py:65-74 (opt-in): dense float32 result of the QSGD codec."""
         L.load()

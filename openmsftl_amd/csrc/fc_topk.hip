@@ -1254,7 +1254,8 @@ struct ResolveArgs {
   WsPtrs W;
   const fc_encode_job* jobs;   // batched encode (see CompactArgs)
   uint64_t ws_stride;
-  float* dense;                // fc_topk_encode_dense: zero the slack of q (one client)
+  float* dense;                // fc_topk_encode_dense: zero the slack of q (one client);
+                               // k_resolve<false, EF>: the residual e' (fc_topk_encode_ef)
   uint32_t rbin;               // 1: k_resolve<true> binned the candidates (the compaction did
                                // not: batched, unfused and rand-k); 0: k_fused_mag did
 };
@@ -1264,7 +1265,11 @@ struct ResolveArgs {
 // 3 per CU) a 64-client batch's 1024 workgroups did not fit one round.
 constexpr int kResolveChunksMax = 1024;
 
-template <bool BIN>
+// EF (fc_topk_encode_ef, fc_ef.hip; one client): a.dense is the new residual e' instead of q.  Its
+// compaction wrote a = g + e at every bracket candidate and +0 only above the bracket; the mirror
+// image of the dense walk zeroes the candidates that END UP selected: those binned above beta by
+// every workgroup before its ticket, those of bin beta at or above T64 by the last arriver.
+template <bool BIN, bool EF = false>
 __global__ __launch_bounds__(kBlock) void k_resolve(ResolveArgs a0) {
   ResolveArgs a = a0;
   apply_job(a);
@@ -1324,7 +1329,7 @@ __global__ __launch_bounds__(kBlock) void k_resolve(ResolveArgs a0) {
     __syncthreads();
   }
   const bool binning = BIN && !retry && rank > 0;         // grid-uniform
-  const bool walk = BIN ? binning : (!retry && (rank > 0 || a.dense));
+  const bool walk = BIN ? binning : (!retry && (rank > 0 || (!EF && a.dense)));
   if (BIN && !binning) return;   // nothing to bin (the gather launch sees the same retry / rank)
   // ---- per-chunk gather sizes: the candidate slot, or (bit 31) the entries slot of a chunk
   // whose candidates overflowed their slot ----
@@ -1458,12 +1463,20 @@ __global__ __launch_bounds__(kBlock) void k_resolve(ResolveArgs a0) {
     // rank == 0 every candidate is slack
     const uint64_t imask = (1ull << a.ib) - 1;
     if (a.dense && walk) {
-      const uint32_t below = rank > 0 ? beta : 0xffffffffu;
-      for_cands(rank > 0, [&](const uint64_t (&v)[kGatherU]) {
+      if constexpr (EF) {                                 // (walk: rank > 0)
+        for_cands(true, [&](const uint64_t (&v)[kGatherU]) {
 #pragma unroll
-        for (int u = 0; u < kGatherU; ++u)
-          if (v[u] != ~0ull && bin_of(v[u]) < below) a.dense[v[u] & imask] = 0.0f;
-      });
+          for (int u = 0; u < kGatherU; ++u)
+            if (v[u] != ~0ull && bin_of(v[u]) > beta) a.dense[v[u] & imask] = 0.0f;
+        });
+      } else {
+        const uint32_t below = rank > 0 ? beta : 0xffffffffu;
+        for_cands(rank > 0, [&](const uint64_t (&v)[kGatherU]) {
+#pragma unroll
+          for (int u = 0; u < kGatherU; ++u)
+            if (v[u] != ~0ull && bin_of(v[u]) < below) a.dense[v[u] & imask] = 0.0f;
+        });
+      }
     }
     if (!last_block_arrive_tree(a.W.tick + kTickWords, gridDim.x, blockIdx.x, &s_flag, 16)) return;
     FC_TR(12);
@@ -1505,9 +1518,16 @@ __global__ __launch_bounds__(kBlock) void k_resolve(ResolveArgs a0) {
     const uint32_t status = retry || other_err ? (uint32_t)FC_STATUS_RETRY_EXACT : (uint32_t)FC_STATUS_OK;
     FC_TR(14);
     if (a.dense && status == FC_STATUS_OK && rank > 0) {
-      for (uint32_t i = (sorted ? first_below : 0u) + tid; i < list_n; i += kBlock) {
-        const uint64_t v = sv[i];
-        if (v < T) a.dense[v & imask] = 0.0f;
+      if constexpr (EF) {                                 // sv[0, first_below) when sorted: >= T
+        for (uint32_t i = tid; i < (sorted ? first_below : list_n); i += kBlock) {
+          const uint64_t v = sv[i];
+          if (v >= T) a.dense[v & imask] = 0.0f;
+        }
+      } else {
+        for (uint32_t i = (sorted ? first_below : 0u) + tid; i < list_n; i += kBlock) {
+          const uint64_t v = sv[i];
+          if (v < T) a.dense[v & imask] = 0.0f;
+        }
       }
     }
     if (!rbin)                                            // the compaction's bins, for the next call
@@ -1526,6 +1546,7 @@ __global__ __launch_bounds__(kBlock) void k_resolve(ResolveArgs a0) {
 }
 template __global__ void k_resolve<true>(ResolveArgs);
 template __global__ void k_resolve<false>(ResolveArgs);
+template __global__ void k_resolve<false, true>(ResolveArgs);
 
 // --------------------------------------------------------------------------------------
 // k_beta: the head of k_resolve<false> alone, for a lone fused packet encode whose gather and

@@ -6,5 +6,6 @@
 #include "fc_qsgd.hip"
 #include "fc_f64.hip"
 #include "fc_capi.hip"
+#include "fc_ef.hip"
 #include "fc_mt.hip"
 #include "fc_perm.hip"
