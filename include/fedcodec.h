@@ -265,7 +265,9 @@ int fc_decode_accumulate(const fc_packet_view* views_dev, int m, int format, uin
                          float* acc, fc_stream_t stream);
 /* Same fold, continuing the partial sum already held in acc (acc = fl(acc + fl(w_i * d_i))
  * for i = 0..m-1): rows of G split across calls or across GPUs (the exact chained reduce of
- * SURVEY.md §8(e)) give the same bits as one call over all rows. */
+ * SURVEY.md §8(e)) give the same bits as one call over all rows.  acc may hold any values: a
+ * -0.0 in it (no +0-started sum produces one) follows the dense sum too, staying -0.0 only where
+ * every term added to it is -0.0. */
 int fc_decode_accumulate_continue(const fc_packet_view* views_dev, int m, int format,
                                   uint64_t n, float* acc, fc_stream_t stream);
 

@@ -640,7 +640,9 @@ __global__ __launch_bounds__(kSBlock, kSBlocksPerCU) void k_decode_sparse(Decode
 // paid a workgroup barrier per (packet, chunk): 2.73 ms per 128 packets of 128 M.)
 // The chunk's quarter offsets of all M packets are loaded once, one packet per lane, and read
 // back with readlane; entries are loaded in groups of kQGroup items, two groups in flight.
-// +0 start, skipped dropped coordinates and NaN-poisoning packets: see k_decode_sparse.
+// +0 start, skipped dropped coordinates and NaN-poisoning packets: see k_decode_sparse.  A
+// continued sum (ACC_IN) that holds -0.0 is the one case where skipping is not exact; the rare
+// fix-up before the write-out restores the dense sum's sign of zero.
 // --------------------------------------------------------------------------------------
 constexpr int kQBlock = 256;
 constexpr int kQuarter = kChunk / 4;
@@ -765,13 +767,19 @@ __global__ __launch_bounds__(kQBlock, 4) void k_fold_q(DecodeArgs a) {
     const fc_packet_hdr* h = (const fc_packet_hdr*)uni_ptr(s_meta[0].hdr);
     if (h->codec == FC_CODEC_DROPOUT_UNBIASED && h->p == 0.0) dz0 = __uint_as_float(0x7fc00000u);
   }
+  bool nz = false;                                  // ACC_IN: the sum to continue holds a -0.0
 #pragma unroll
   for (int i = 0; i < kQuarter / 256; ++i) {
     const uint32_t loc = (uint32_t)(i * 256 + lane * 4);
     float4 v = make_float4(dz0, dz0, dz0, dz0);
-    if (ACC_IN) v = load4(reinterpret_cast<const float*>(a.out), (uint64_t)qbase + loc, a.n);
+    if (ACC_IN) {
+      v = load4(reinterpret_cast<const float*>(a.out), (uint64_t)qbase + loc, a.n);
+      nz |= (__float_as_uint(v.x) == 0x80000000u) | (__float_as_uint(v.y) == 0x80000000u) |
+            (__float_as_uint(v.z) == 0x80000000u) | (__float_as_uint(v.w) == 0x80000000u);
+    }
     *reinterpret_cast<float4*>(&qt[loc]) = v;
   }
+  const bool neg0_in = ACC_IN && __any(nz);         // wave-uniform; never true for a sum a fold made
   if (slow || dense_q) {
     // ---- slow body (a launch holding rand-k Philox, dropout-unbiased or NaN-poisoning
     // packets, or a quarter with more than kQR * 64 entries): item by item, every rule per
@@ -896,6 +904,40 @@ __global__ __launch_bounds__(kQBlock, 4) void k_fold_q(DecodeArgs a) {
       if (m0 + kQGroup >= M) break;                                // uniform
       issue(0, m0 + 2 * kQGroup);
       process(1, m0 + kQGroup);
+    }
+  }
+  if (neg0_in) {
+    // ---- the continued sum held -0.0 (rare: a +0-started sum never does; a caller's own acc
+    // may).  Skipping a dropped coordinate's term fl(+0 * w) is exact except for acc = -0.0 and
+    // a term of +0: -0 + +0 = +0.  A coordinate that is still -0.0 here has been -0.0 all along
+    // (every term folded into it was -0.0), so the dense sum of gar.py:44 leaves it -0.0 only if
+    // no packet with a sign-positive weight dropped it: mark what each such packet keeps and
+    // turn the unmarked -0.0 into +0 ----
+    for (uint32_t m = 0; m < M; ++m) {
+      const QMeta& pm = s_meta[m];
+      const float w = __uint_as_float(uni32(__float_as_uint(pm.w)));
+      if (__float_as_uint(w) >> 31) continue;       // fl(+0 * w) = -0: skipping it was exact
+      uint32_t st, en;
+      range(m, st, en);
+      const fc_packet_hdr* h = (const fc_packet_hdr*)uni_ptr(pm.hdr);
+      PktCache pk;
+      pk.thresh = uni64(pm.thresh); pk.ib = uni32(pm.flags) & 0xffu;
+      pk.codec = (uni32(pm.flags) >> 8) & 0xffu; pk.key_mode = (uni32(pm.flags) >> 16) & 0xffu;
+      pk.seed = h->seed; pk.offset = h->offset; pk.p = h->p;
+      gu16* pidx = (gu16*)uni_ptr(pm.idx) + base;
+      gf32* pval = (gf32*)uni_ptr(pm.val) + base;
+      s_mark[q][lane] = 0u;                         // (the fast body's dummy slots)
+      for (uint32_t e = st + lane; e < en; e += 64) {
+        const uint32_t id = (uint32_t)base + pidx[e];
+        const uint32_t loc = id - qbase;
+        if (loc < (uint32_t)kQuarter && entry_kept(pk, id, pval[e]))
+          atomicOr(&s_mark[q][loc >> 5], 1u << (loc & 31));
+      }
+      const uint32_t bits = s_mark[q][lane];
+      for (int b = 0; b < 32; ++b)
+        if (!((bits >> b) & 1u) && __float_as_uint(qt[lane * 32 + b]) == 0x80000000u)
+          qt[lane * 32 + b] = 0.0f;
+      s_mark[q][lane] = 0u;
     }
   }
   // ---- write the quarter out ----
