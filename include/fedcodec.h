@@ -231,6 +231,28 @@ int fc_topk_encode_batch(const fc_encode_job* jobs_dev, int m, uint64_t n, uint6
 int fc_topk_encode_batch_part(const fc_encode_job* jobs_dev, int m, uint64_t n, uint64_t k,
                               int key_mode, uint64_t capacity, void* ws, size_t ws_bytes,
                               int part, fc_stream_t stream);
+/* ---- batched top-k with error feedback: fc_topk_encode_ef for m clients ---------------
+ * Client c: a_c = fl32(jobs[c].g + ef[c].res_in), one IEEE add per element; packet c is the one
+ * fc_topk_encode_batch writes for a_c (so also fc_topk_encode_ef's, bit for bit); ef[c].res_out
+ * is +0.0f at the k selected coordinates and a_c elsewhere.  Magnitude keys only: the jobs' seed
+ * and offset are ignored (the headers carry 0).  Launches for the whole batch: pilot, sample,
+ * compaction, two resolves; none waits in-kernel for another workgroup (last-arriver tickets
+ * only), so there is no fc_fused_order_* handling.  ws: fc_workspace_bytes_batch(n, m), zeroed
+ * once.  Needs 1 <= m <= 65535 and 0 < k < n.
+ * Both tables are DEVICE memory, so the library cannot look inside them: 16-B alignment of every
+ * g / res_in / res_out, their length n, and that no res_out overlaps any g, res_in or other
+ * res_out of the batch are the caller's contract.  What the host can see (NULL tables, m, k,
+ * capacity: FC_ERR_ARG; a short workspace: FC_ERR_WORKSPACE) is reported before the GPU is
+ * touched.
+ * A header with FC_STATUS_RETRY_EXACT: THAT client's packet and res_out are not valid; run
+ * fc_ef_sum -> fc_topk_encode_exact -> fc_ef_clear for it alone.  Other clients are unaffected. */
+typedef struct fc_ef_job {
+  const float* res_in;   /* residual e (16-B aligned, n floats); never written            */
+  float*       res_out;  /* new residual e'; must not overlap any g / res_in / res_out of the batch */
+} fc_ef_job;             /* 16 bytes; entry c belongs to jobs[c] */
+int fc_topk_encode_ef_batch(const fc_encode_job* jobs_dev, const fc_ef_job* ef_dev, int m,
+                            uint64_t n, uint64_t k, uint64_t capacity,
+                            void* ws, size_t ws_bytes, fc_stream_t stream);
 
 /* Exact radix-select path (several reads of g); always succeeds; n_entries == k. */
 int fc_topk_encode_exact(const float* g, uint64_t n, uint64_t k, int key_mode, uint64_t seed,

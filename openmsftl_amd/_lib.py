@@ -58,6 +58,11 @@ class EncodeJob(ctypes.Structure):
                 ("qoff", ctypes.c_void_p)]
 
 
+class EfJob(ctypes.Structure):
+    """fc_ef_job: entry c is the residual pair of EncodeJob c (fc_topk_encode_ef_batch)."""
+    _fields_ = [("res_in", ctypes.c_void_p), ("res_out", ctypes.c_void_p)]
+
+
 class PermState(ctypes.Structure):
     """fc_perm_state: the device state block of fc_mt_permutation."""
     _fields_ = [("key", ctypes.c_uint32 * 624), ("pos", ctypes.c_uint32),
@@ -68,6 +73,7 @@ class PermState(ctypes.Structure):
 assert ctypes.sizeof(PermState) == 2520
 assert ctypes.sizeof(PacketHdr) == HDR_BYTES
 assert ctypes.sizeof(EncodeJob) == 64
+assert ctypes.sizeof(EfJob) == 16
 assert ctypes.sizeof(PacketView) == 56
 
 _u64, _i32, _sz, _vp, _dbl = (ctypes.c_uint64, ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p,
@@ -89,6 +95,7 @@ SIGNATURES = {
                                      _vp, _vp]),
     "fc_topk_encode_ef": (_i32, [_vp, _vp, _vp, _u64, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp,
                                  _sz, _vp]),
+    "fc_topk_encode_ef_batch": (_i32, [_vp, _vp, _i32, _u64, _u64, _u64, _vp, _sz, _vp]),
     "fc_ef_sum": (_i32, [_vp, _vp, _vp, _u64, _vp]),
     "fc_ef_clear": (_i32, [ctypes.POINTER(PacketView), _u64, _vp, _vp]),
     "fc_workspace_bytes_batch": (_sz, [_u64, _i32]),

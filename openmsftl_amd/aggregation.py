@@ -26,6 +26,10 @@ GAR (gar.py:44).  Here the rows never become a dense matrix on the common path:
   RNG draws as the reference, the same exceptions at the same row), each row cast to G's dtype
   and folded at once into the GAR's sum in NumPy's promoted dtype (``fold_rows``: one row of
   device memory); only a merge (hierarchies) or a host GAR stacks the rows into G.
+* opt-in (``aggregation_config["batched_error_feedback"]``): a round whose clients ALL compress
+  with 'top' and error feedback takes the "ef-batch" route (:func:`ef_batch_k`,
+  :func:`ef_batch_fold`): groups of <= 64 clients encoded by one fc_topk_encode_ef_batch launch
+  chain and folded in row order, the same bits as the generic path.
 
 ``aggregate_grads`` is a plain function so that :func:`openmsftl_amd.integration.install` can
 bind it onto the REFERENCE ``Aggregator`` class (its ``self.gar`` may then be a reference GAR
@@ -390,6 +394,84 @@ def fold_rows(gar, clients, n: int, tdt: torch.dtype, dev: torch.device) -> torc
     return acc
 
 
+#: clients per batched error-feedback encode at most (k_compact_mag1's interleave group)
+EF_BATCH_GROUP = 64
+
+
+def ef_batch_k(agg, clients) -> Optional[int]:
+    """k when the round may take the opt-in "ef-batch" route, else None (today's routing):
+    ``aggregation_config["batched_error_feedback"]`` is set, the GAR is the device FedAvg with
+    float32 (or no) weights, no hierarchies, one device, and EVERY client is the drop-in
+    Compression with 'top', error feedback on and one common fraction with 0 < k < n, on 1-D
+    float32 gradients of one length.  Touches no GPU."""
+    cfg = getattr(agg, "aggregation_config", None) or {}
+    if not cfg.get("batched_error_feedback", False) or not clients:
+        return None
+    if type(agg.gar) is not FedAvg or agg.num_hierarchies != 0:
+        return None
+    if cfg.get("devices", DEFAULT_DEVICES) not in (None, 1):      # multi-GPU rounds: dense-fold
+        return None
+    w = getattr(agg.gar, "gradient_weights", None)
+    if w is not None and np.asarray(w).dtype != np.float32:
+        return None
+    n, fr = None, None
+    for c in clients:
+        C, g = c.C, np.asarray(c.grad)
+        if not isinstance(C, Compression) or C.compression_function != "top" or not C.error_feedback:
+            return None
+        if g.ndim != 1 or g.dtype != np.float32 or (n is not None and g.shape[0] != n):
+            return None
+        f = C.fraction_coordinates
+        if not isinstance(f, (int, float, np.floating, np.integer)) or not np.isfinite(f):
+            return None
+        if fr is not None and f != fr:
+            return None
+        n, fr = g.shape[0], f
+    k = kept_count(fr, n)
+    return k if 0 < k < n else None
+
+
+def ef_batch_group(agg, n: int, m: int, dev: torch.device) -> int:
+    """Clients per group of the "ef-batch" route: each holds its gradient and spare residual (4N
+    each), a reserved packet and an encoder workspace; the aggregate (4N) is held once."""
+    from .pipeline import packet_bytes
+    per = 8 * n + packet_bytes(n) + int(L.load().fc_workspace_bytes(n))
+    fit = (_budget(agg, dev) - 4 * n) // per
+    return int(max(1, min(EF_BATCH_GROUP, m, fit)))
+
+
+def ef_batch_fold(agg, clients, n: int, k: int, weights: np.ndarray, dev: torch.device) -> torch.Tensor:
+    """FedAVG of the rows ``compress()`` would make for a round of error-feedback 'top' clients,
+    group by group in row order: upload, ONE batched encode (codec.encode_top_ef_batch), one
+    resolve, the group's packets folded into the running sum, then the group's residuals
+    committed.  A client's residual advances once per round and only after its group resolved."""
+    for c in clients:                         # a bad residual raises before anything advances
+        c.C._ef_buffers(n, dev, allocate=False)
+    m = len(clients)
+    gsz = ef_batch_group(agg, n, m, dev)
+    cache = agg.__dict__.setdefault("_ef_batch_packets", {})
+    packets = cache.get((n, dev))
+    if packets is None or len(packets) < gsz:
+        cache.clear()
+        packets = cache[(n, dev)] = codec.Packet.alloc_batch(n, gsz, L.FC_FMT_IDXVAL, dev, k=k)
+    acc = torch.empty(n, dtype=torch.float32, device=dev)
+    for gi, s in enumerate(range(0, m, gsz)):
+        rows = clients[s:s + gsz]
+        grads = [torch.from_numpy(np.ascontiguousarray(c.grad)).to(dev) for c in rows]
+        bufs = [c.C._ef_buffers(n, dev) for c in rows]
+        pk = packets[:len(rows)]
+        codec.encode_top_ef_batch(grads, [b[0] for b in bufs], k,
+                                  residuals_out=[b[1] for b in bufs], packets=pk, check=False)
+        codec.resolve(pk)
+        codec.decode_accumulate(pk, [float(x) for x in weights[s:s + len(rows)]], out=acc,
+                                continue_sum=gi > 0)
+        for c, (res, new) in zip(rows, bufs):
+            c.C._ef_commit(res, new, True)
+        for p in pk:
+            p.release()
+    return acc
+
+
 def aggregate_grads(self, clients: List, input_feature: np.ndarray = None,
                     val_loader=None) -> None:
     """aggregation.py:54-78 on the device: sets ``self.agg_grad`` (host array) and
@@ -406,6 +488,14 @@ def aggregate_grads(self, clients: List, input_feature: np.ndarray = None,
     n = grad0.shape[0]
     if any(np.asarray(c.grad).shape != (n,) for c in clients):
         raise ValueError("client gradients must share one length (aggregation.py:61)")
+    k_ef = ef_batch_k(self, clients)
+    if k_ef is not None:
+        # opt-in: a round of error-feedback 'top' clients, batched (dense-fold's bits)
+        self.agg_path = "ef-batch"
+        self.curr_G = None
+        w = self.gar._weights(len(clients), np.float32)             # gar.py:37-42 (persisted)
+        self.agg_grad = ef_batch_fold(self, clients, n, k_ef, w, dev).cpu().numpy()
+        return
     device_gar = hasattr(self.gar, "aggregate_packets")
     w = getattr(self.gar, "gradient_weights", None)
     f32_weights = w is None or np.asarray(w).dtype == np.float32
@@ -493,7 +583,7 @@ class Aggregator:
         self.gar = self.__get_gar()
         self.curr_G = None
         self.agg_grad = None
-        self.agg_path = None                # "stream" | "dense-fold" | "dense": the last call's path
+        self.agg_path = None                # "stream" | "dense-fold" | "dense" | "ef-batch": the last call's path
         self.agg_draws = None               # streamed np.random draws: "device-mt" | "device-perm" | "host" | None
         self.analyze_pc = self.aggregation_config.get("pc_analysis", False)
         self.num_hierarchies = self.aggregation_config.get("num_hierarchies", 0)

@@ -14,6 +14,7 @@ Plus per-chunk counts and quarter offsets and a 96-byte device header (``fc_pack
 """
 from __future__ import annotations
 
+import bisect
 import ctypes
 import threading
 import weakref
@@ -507,6 +508,97 @@ def encode_top_batch(grads: Sequence[torch.Tensor], k: int, *,
     if check:
         resolve(packets)
     return list(packets)
+
+
+def ef_jobs(residuals: Sequence[torch.Tensor], residuals_out: Sequence[torch.Tensor]) -> torch.Tensor:
+    """Device array of fc_ef_job, entry c beside :func:`encode_jobs`' entry c (build once, reuse
+    while the buffers live)."""
+    arr = (L.EfJob * len(residuals))(*[L.EfJob(res_in=r.data_ptr(), res_out=o.data_ptr())
+                                       for r, o in zip(residuals, residuals_out)])
+    host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
+    return host.to(residuals_out[0].device)
+
+
+_ef_jobs = ef_jobs        # (encode_top_ef_batch has a keyword of that name)
+
+
+def encode_top_ef_batch(grads: Sequence[torch.Tensor], residuals: Sequence[Optional[torch.Tensor]],
+                        k: int, *, residuals_out: Optional[Sequence[torch.Tensor]] = None,
+                        packets: Optional[Sequence[Packet]] = None,
+                        jobs: Optional[torch.Tensor] = None,
+                        ef_jobs: Optional[torch.Tensor] = None, check: bool = True):
+    """:func:`encode_top_ef` for M equal-length gradients in ONE launch per pipeline stage
+    (fc_topk_encode_ef_batch): client c's packet and ``residuals_out[c]`` are, bit for bit, what
+    ``encode_top_ef(grads[c], residuals[c], k)`` gives.  Returns ``(packets, residuals_out)``.
+
+    A ``None`` entry of ``residuals`` means zeros.  No ``residuals_out[i]`` may overlap any
+    gradient, residual or other output of the batch (ValueError before any launch).  ``jobs`` /
+    ``ef_jobs``: prebuilt :func:`encode_jobs` / :func:`ef_jobs` tables for these exact buffers.
+    ``check=True`` reads the headers once and runs the exact chain for exactly the clients whose
+    bracket missed (``packet.retried``); with ``check=False`` call :func:`resolve` later.
+    k = 0, k = n and n < 2 loop over :func:`encode_top_ef`."""
+    if not grads:
+        raise ValueError("no gradients")
+    m = len(grads)
+    n, dev = grads[0].numel(), grads[0].device
+    if len(residuals) != m or (residuals_out is not None and len(residuals_out) != m):
+        raise ValueError("one residual and one output per gradient")
+    if packets is not None and len(packets) != m:
+        raise ValueError("one packet per gradient")
+    if n == 0:
+        raise ValueError("empty gradient")
+    if not 0 <= k <= n:
+        raise ValueError(f"k={k} outside [0, {n}]")
+    if any(r is None for r in residuals):            # one shared block of zeros (never written)
+        zeros = torch.zeros(n, dtype=torch.float32, device=dev)
+        residuals = [zeros if r is None else r for r in residuals]
+    if residuals_out is None:
+        residuals_out = [torch.empty(n, dtype=torch.float32, device=dev) for _ in range(m)]
+    for i in range(m):
+        for t, name in ((grads[i], "g"), (residuals[i], "residual"),
+                        (residuals_out[i], "residual_out")):
+            _require_cuda_f32(t, f"{name}[{i}]")
+            if t.numel() != n or t.device != dev:
+                raise ValueError(f"{name}[{i}] must have {n} elements on {dev}")
+    # address ranges on the host: an output against every input and every other output
+    nb = 4 * n
+    outs = sorted((o.data_ptr(), i) for i, o in enumerate(residuals_out))
+    for (a, i), (b, j) in zip(outs, outs[1:]):
+        if b < a + nb:
+            raise ValueError(f"residuals_out[{i}] and residuals_out[{j}] overlap")
+    starts = [a for a, _ in outs]
+    for kind, ts in (("grads", grads), ("residuals", residuals)):
+        for j, t in enumerate(ts):
+            p = t.data_ptr()
+            lo = bisect.bisect_right(starts, p - nb)         # first output starting after p - nb
+            if lo < m and starts[lo] < p + nb:
+                raise ValueError(f"residuals_out[{outs[lo][1]}] overlaps {kind}[{j}]")
+    if packets is None:
+        packets = [Packet.alloc(n, L.FC_FMT_IDXVAL, dev, k=k) for _ in range(m)]
+    if k == 0 or k == n or n < 2:                    # trivial thresholds: the exact chain per client
+        for g, r, o, p in zip(grads, residuals, residuals_out, packets):
+            encode_top_ef(g, r, k, residual_out=o, packet=p, check=check)
+        return list(packets), list(residuals_out)
+    lib = L.load()
+    cap = int(lib.fc_packet_capacity(n))
+    for p, g, r, o in zip(packets, grads, residuals, residuals_out):
+        if p.capacity < cap or p.fmt != L.FC_FMT_IDXVAL:
+            raise ValueError("packet too small or not idx/val")
+        p.k = k
+        p._enc = ("ef", g, r, o, k)
+        p._dense_only = False
+        p.retried = False
+    if jobs is None:
+        jobs = encode_jobs(grads, packets)
+    if ef_jobs is None:
+        ef_jobs = _ef_jobs(residuals, residuals_out)
+    ws = BatchWorkspace.get(n, m, dev)
+    L.check(lib.fc_topk_encode_ef_batch(_vp(jobs), _vp(ef_jobs), m, n, k, packets[0].capacity,
+                                        _vp(ws.buf), ws.nbytes, _stream(dev)),
+            "fc_topk_encode_ef_batch")
+    if check:
+        resolve(packets)
+    return list(packets), list(residuals_out)
 
 
 def encode_fold_batch(grads: Sequence[torch.Tensor], k: int, weights, out: torch.Tensor, *,

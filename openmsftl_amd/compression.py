@@ -239,6 +239,31 @@ class Compression:
         out = codec.decode(pkt)
         return out if on_device else out.cpu().numpy()
 
+    # the two hooks of a batch driver (aggregation's "ef-batch" route): the state advances
+    # exactly once per round, in _ef_commit, and not at all when the round fails before it
+    def _ef_buffers(self, n: int, device: torch.device, allocate: bool = True):
+        """``(residual or zeros, spare buffer)`` for a gradient of n elements on ``device``,
+        with _top_ef's validation (``allocate=False``: the validation alone); nothing is stored
+        until :meth:`_ef_commit`."""
+        res = self._residual
+        if res is not None and (res.numel() != n or res.device != device):
+            raise ValueError(f"error_feedback: gradient of {n} elements on {device}, residual "
+                             f"of {res.numel()} on {res.device} (reset_residual() starts over)")
+        if not allocate:
+            return None
+        if res is None:
+            res = torch.zeros(n, dtype=torch.float32, device=device)
+        spare = self._residual_spare
+        if spare is None or spare.numel() != n or spare.device != device:
+            spare = torch.empty(n, dtype=torch.float32, device=device)
+        return res, spare
+
+    def _ef_commit(self, res: torch.Tensor, new: torch.Tensor, numpy_kind: bool) -> None:
+        """``new`` (the spare _ef_buffers handed out, now written) becomes the residual and
+        ``res`` the next spare."""
+        self._residual, self._residual_spare = new, res
+        self._residual_numpy = numpy_kind
+
     def get_residual(self):
         """A copy of the error-feedback residual, of the kind of the last input (NumPy array or
         CUDA tensor); None before the first call."""

@@ -16,6 +16,14 @@
 // Nothing here waits in-kernel for another workgroup (last-arriver tickets only), so the call
 // runs beside any other kernel.  The exact fallback (header status RETRY_EXACT, whose e' is not
 // valid) is fc_ef_sum -> fc_topk_encode_exact on the sum -> fc_ef_clear.
+//
+// The batched form (fc_topk_encode_ef_batch) is fc_topk_encode_batch's chain on a_c = g_c + e_c
+// for m clients, the pairs (e_c, e'_c) in a second device table (fc_ef_job) beside the jobs:
+//
+//   k_pilot_ef            k_pilot over EfSrc: one workgroup per client, the window in win_flag
+//   k_sample1_ef_batch    k_sample1<kKeyMag, true>'s body over EfSrc, grid.y = client
+//   k_compact_mag1_ef_batch   the pass above in k_compact_mag1's batched geometry (mag_item_of)
+//   k_resolve<true>, k_resolve<false, EF>   grid.y = client, e' from ef[client].res_out
 #include "fc_state.h"
 
 namespace fc {
@@ -40,6 +48,34 @@ __global__ __launch_bounds__(kBlock, 8) void k_sample1_ef(const float* __restric
   const EfSrc src{g, e};
   sample_body<kKeyMag, false, EfSrc, false>(&src, P, 0ull, 0ull, W, ib, hdr, HI, blockIdx.x, gridDim.x,
                                             false, sm, 0u);
+}
+
+// The batched pilot and sample: k_pilot / k_sample1<kKeyMag, true> with the source of client
+// blockIdx.x / blockIdx.y taken from the two job tables.  Magnitude keys: no seed, no offset.
+__global__ __launch_bounds__(kBlock) void k_pilot_ef(SamplePlan P, WsPtrs W, const fc_encode_job* jobs,
+                                                     const fc_ef_job* ef, uint64_t ws_stride) {
+  __shared__ uint32_t h[kHistBins];
+  __shared__ uint32_t s_tmp[8], s_out[4];
+  const EfSrc src{jobs[blockIdx.x].g, ef[blockIdx.x].res_in};
+  W = ws_shift(W, (uint64_t)blockIdx.x * ws_stride);
+  for (int b = threadIdx.x; b < kHistBins; b += kBlock) h[b] = 0;
+  float4 xs[kSampleSegs];
+  uint32_t es[kSampleSegs], ls[kSampleSegs];
+#pragma unroll
+  for (int q = 0; q < kSampleSegs; ++q) { xs[q] = make_float4(0.f, 0.f, 0.f, 0.f); es[q] = ls[q] = 0; }
+  const FineWin F = pilot_window<kKeyMag, false, EfSrc>(&src, P, 0ull, 0ull, h, s_tmp, s_out, false, xs, es, ls);
+  if (threadIdx.x == 0) W.st->win_flag = 0x80000000u | ((F.khi >> 19) << 12) | (F.klo >> 19);
+}
+
+__global__ __launch_bounds__(kBlock, 8) void k_sample1_ef_batch(SamplePlan P, WsPtrs W, uint32_t ib,
+                                                             HdrInit HI, const fc_encode_job* jobs,
+                                                             const fc_ef_job* ef, uint64_t ws_stride) {
+  __shared__ SampleShared sm;
+  const fc_encode_job& J = jobs[blockIdx.y];
+  const EfSrc src{J.g, ef[blockIdx.y].res_in};
+  W = ws_shift(W, (uint64_t)blockIdx.y * ws_stride);
+  sample_body<kKeyMag, false, EfSrc, true>(&src, P, 0ull, 0ull, W, ib, J.hdr, HI, blockIdx.x, gridDim.x,
+                                           false, sm, 0u);
 }
 
 // The two residual pointers travel beside CompactArgs (which the other compactions share).
@@ -80,17 +116,17 @@ __device__ __forceinline__ void ef_add(const float* e, uint32_t chunk, uint64_t 
 //                bits) compact_mag_body<false> re-reads values through MagOut::g: a is stored to
 //                e' first and MagOut::g points there (each lane re-reads only what it stored
 //                itself), then the elements above the bracket are overwritten with +0.
-__global__ __launch_bounds__(kCBlock, FC_MAG1_WAVES_PER_EU) void k_compact_mag1_ef(CompactArgs a0,
-                                                                                  EfArgs ef) {
+// (client: the batched launch's; a lone call's is 0 with a0.jobs == nullptr)
+__device__ __forceinline__ void compact_mag_ef_wg(const CompactArgs& a0, const float* g,
+                                                  const EfArgs& ef, uint32_t client, uint32_t chunk) {
   constexpr int NW = 8, NQ = MagGeo<NW>::kQ, IS = MagGeo<NW>::kIStride;
   __shared__ __attribute__((aligned(16))) MagShared sh;
   const int tid = threadIdx.x;
-  const uint32_t chunk = blockIdx.x;
   float x[NQ];
-  mag_load<NW>(a0.g, chunk, a0.n, x);
+  mag_load<NW>(g, chunk, a0.n, x);
   ef_add<NW>(ef.res_in, chunk, a0.n, x);                    // a = fl32(g + e)
-  const MagState st = mag_state(a0.W.st);
-  MagOut o = mag_out(a0, 0u);
+  const MagState st = mag_state(mag_S(a0, client));
+  MagOut o = mag_out(a0, client);
   FC_G float* ro = (FC_G float*)ef.res_out;
   const uint32_t base = chunk * (uint32_t)kChunk;
   const uint32_t l0 = (uint32_t)((tid >> 6) * 256 + lane_id());
@@ -140,6 +176,35 @@ __global__ __launch_bounds__(kCBlock, FC_MAG1_WAVES_PER_EU) void k_compact_mag1_
     for (int q = 0; q < NQ; ++q)                          // bit 1 listed, bit 0 candidate
       if (__float_as_uint(x[q]) == 2u) ro[base + l0 + (q >> 2) * IS + (q & 3) * 64] = 0.0f;
   }
+}
+__global__ __launch_bounds__(kCBlock, FC_MAG1_WAVES_PER_EU) void k_compact_mag1_ef(CompactArgs a0,
+                                                                                  EfArgs ef) {
+  compact_mag_ef_wg(a0, a0.g, ef, 0u, blockIdx.x);
+}
+
+// The batched launch: k_compact_mag1's geometry (mag_item_of: 64 clients' chunks interleaved in a
+// 3-D grid, the linear grid above 65,535 chunks), the client's gradient and residual pair read
+// from the two tables in one scalar round trip ahead of the loads (through the scalar cache, as
+// mag_out reads the job: no kernel of the chain writes either table).
+__device__ __forceinline__ void ef_item_ptrs(const CompactArgs& a0, const fc_ef_job* ef, uint32_t client,
+                                             const float*& g, EfArgs& r) {
+  fc_u32x2 gv;
+  fc_u32x4 ev;
+  asm volatile("s_load_dwordx2 %0, %2, 0x0\n\ts_load_dwordx4 %1, %3, 0x0\n\ts_waitcnt lgkmcnt(0)"
+               : "=&s"(gv), "=&s"(ev) : "s"(&a0.jobs[client].g), "s"(&ef[client]) : "memory");
+  g = as_ptr<const float>(gv.x, gv.y);
+  r.res_in = as_ptr<const float>(ev.x, ev.y);
+  r.res_out = as_ptr<float>(ev.z, ev.w);
+}
+__global__ __launch_bounds__(kCBlock, FC_MAG1_WAVES_PER_EU) void k_compact_mag1_ef_batch(
+    CompactArgs a0, const fc_ef_job* ef) {
+  uint32_t client, chunk;
+  mag_item_of(a0, client, chunk);
+  if (client >= a0.m) return;                            // a partial last group
+  const float* g;
+  EfArgs r;
+  ef_item_ptrs(a0, ef, client, g, r);
+  compact_mag_ef_wg(a0, g, r, client, chunk);
 }
 
 // ---- the exact fallback's two streaming passes -------------------------------------------
@@ -266,6 +331,66 @@ int fc_topk_encode_ef(const float* g, const float* res_in, float* res_out, uint6
   hipLaunchKernelGGL(k_resolve<true>, grid, dim3(kBlock), 0, s, ra);
   FC_LAUNCHED("k_resolve<bin>");
   hipLaunchKernelGGL((k_resolve<false, true>), grid, dim3(kBlock), 0, s, ra);
+  FC_LAUNCHED("k_resolve<gather, ef>");
+  return FC_OK;
+}
+
+int fc_topk_encode_ef_batch(const fc_encode_job* jobs, const fc_ef_job* ef, int m, uint64_t n,
+                            uint64_t k, uint64_t capacity, void* ws, size_t ws_bytes,
+                            fc_stream_t stream) {
+  // fc_topk_encode_batch_part's checks (the tables are device memory: their contents are the
+  // caller's contract)
+  FC_CHECK(jobs != nullptr, "jobs is NULL");
+  FC_CHECK(ef != nullptr, "ef jobs is NULL");
+  FC_CHECK(m >= 1 && m <= 65535, "m=%d outside [1, 65535]", m);
+  FC_CHECK(n >= 2 && n <= 0xffffffffull, "n=%llu outside [2, 2^32-1]", (unsigned long long)n);
+  FC_CHECK(k > 0 && k < n, "batched error-feedback encode needs 0 < k < n (k=%llu): trivial k is "
+           "fc_ef_sum + fc_topk_encode_exact + fc_ef_clear per client", (unsigned long long)k);
+  FC_CHECK(capacity >= fc_packet_capacity(n), "capacity %llu < fc_packet_capacity(n) %llu",
+           (unsigned long long)capacity, (unsigned long long)fc_packet_capacity(n));
+  FC_CHECK(ws != nullptr, "workspace is NULL");
+  if (ws_bytes < fc_workspace_bytes_batch(n, m))
+    return fail(FC_ERR_WORKSPACE, "workspace %zu B < %zu B needed", ws_bytes,
+                fc_workspace_bytes_batch(n, m));
+  const uint32_t ib = index_bits(n);
+  const uint64_t stride = WsLayout::of(n).bytes;
+  HdrInit hi;
+  memset(&hi, 0, sizeof hi);
+  hi.n = (uint32_t)n; hi.k = (uint32_t)k; hi.ib = ib;
+  hi.codec = FC_CODEC_TOP; hi.format = FC_FMT_IDXVAL; hi.key_mode = FC_KEY_MAGNITUDE;
+  CompactArgs ca;
+  memset(&ca, 0, sizeof ca);
+  ca.n = n; ca.ib = ib; ca.nchunks = num_chunks(n); ca.W = ws_ptrs(ws, n); ca.HI = hi;
+  ca.jobs = jobs; ca.ws_stride = stride;
+  ResolveArgs ra;
+  memset(&ra, 0, sizeof ra);
+  ra.ib = ib; ra.nchunks = ca.nchunks; ra.k = k; ra.key_mode = FC_KEY_MAGNITUDE;
+  ra.W = ca.W; ra.jobs = jobs; ra.ws_stride = stride; ra.ef = ef;
+  ra.rbin = 1;                       // k_resolve<true> bins the candidates
+  hipStream_t s = (hipStream_t)stream;
+  // fc_topk_encode_batch's plan (cbins_log2 and FC_SAMPLE_ROUNDS included): the same bracket,
+  // and so the same slack entries, as it lists for a
+  SamplePlan P = make_plan(n, k);
+  P.cbins_log2 = cand_bins_log2(n, P);
+  const dim3 sgrid((P.pstride + FC_SAMPLE_ROUNDS - 1) / FC_SAMPLE_ROUNDS, (uint32_t)m);
+  {
+    TimedLaunch t(FC_TIME_SAMPLE, s);
+    hipLaunchKernelGGL(k_pilot_ef, dim3((uint32_t)m), dim3(kBlock), 0, s, P, ca.W, jobs, ef, stride);
+    FC_LAUNCHED("k_pilot_ef");
+    hipLaunchKernelGGL(k_sample1_ef_batch, sgrid, dim3(kBlock), 0, s, P, ca.W, ib, hi, jobs, ef, stride);
+    FC_LAUNCHED("k_sample1_ef_batch");
+  }
+  {
+    TimedLaunch t(FC_TIME_COMPACT, s);
+    const dim3 grid = compact_mag_grid(ca, (uint32_t)m);
+    hipLaunchKernelGGL(k_compact_mag1_ef_batch, grid, dim3(kCBlock), 0, s, ca, ef);
+    FC_LAUNCHED("k_compact_mag1_ef_batch");
+  }
+  const dim3 rgrid(resolve_grid(ca.nchunks, kResolveGridBatch), (uint32_t)m);
+  TimedLaunch t(FC_TIME_ENGINE, s);
+  hipLaunchKernelGGL(k_resolve<true>, rgrid, dim3(kBlock), 0, s, ra);
+  FC_LAUNCHED("k_resolve<bin>");
+  hipLaunchKernelGGL((k_resolve<false, true>), rgrid, dim3(kBlock), 0, s, ra);
   FC_LAUNCHED("k_resolve<gather, ef>");
   return FC_OK;
 }

@@ -575,10 +575,11 @@ struct CompactArgs {
 };
 
 // Per-client fields of a batched launch (jobs[blockIdx.y]); no-op for a single client.
-template <typename Args>
+template <typename Args, bool EF = false>
 __device__ __forceinline__ void apply_job(Args& a) {
   if (!a.jobs) return;
   const fc_encode_job& J = a.jobs[blockIdx.y];
+  if constexpr (EF) a.dense = a.ef[blockIdx.y].res_out;   // batched k_resolve<false, EF>
   a.idx = J.idx; a.val = J.val; a.cnt = J.cnt; a.hdr = J.hdr;
   if constexpr (std::is_same<Args, CompactArgs>::value) a.qoff = J.qoff;
   a.seed = J.seed; a.offset = J.offset;
@@ -1258,6 +1259,7 @@ struct ResolveArgs {
                                // k_resolve<false, EF>: the residual e' (fc_topk_encode_ef)
   uint32_t rbin;               // 1: k_resolve<true> binned the candidates (the compaction did
                                // not: batched, unfused and rand-k); 0: k_fused_mag did
+  const fc_ef_job* ef;         // batched k_resolve<false, EF>: client blockIdx.y's e' (dense)
 };
 
 // chunks per workgroup (their gather sizes live in LDS; the launches size the grid so that no
@@ -1272,7 +1274,7 @@ constexpr int kResolveChunksMax = 1024;
 template <bool BIN, bool EF = false>
 __global__ __launch_bounds__(kBlock) void k_resolve(ResolveArgs a0) {
   ResolveArgs a = a0;
-  apply_job(a);
+  apply_job<ResolveArgs, EF>(a);
   __shared__ uint64_t sv[kSmallCap];                      // 32 KiB: histogram, then sort
   __shared__ uint32_t s_pre[kResolveChunksMax];           // per-chunk gather sizes
   __shared__ uint32_t s_tmp[8], s_out[4], s_flag, s_cnt, s_base, s_tot[2];
