@@ -293,6 +293,39 @@ int fc_decode_accumulate(const fc_packet_view* views_dev, int m, int format, uin
 int fc_decode_accumulate_continue(const fc_packet_view* views_dev, int m, int format,
                                   uint64_t n, float* acc, fc_stream_t stream);
 
+/* ---- Gram matrix of a round's packets: G G^T in float64 without the dense G ---------------
+ * What a geometry-aware rule needs of the clients (Krum's distances gar.py:184-212,
+ * |g_i - g_j|^2 = G_ii + G_jj - 2 G_ij; pc_analysis' singular values aggregation.py:64-67, the
+ * square roots of the eigenvalues) computed straight from the packets (fc_gram.hip).
+ * views_dev: DEVICE array of m FC_FMT_IDXVAL views with qoff present, as fc_decode_accumulate
+ *   takes them; `weight` is ignored.  1 <= m <= FC_GRAM_MAX_M.
+ * d_i: the float32 row fc_decode_dense produces for packet i: an entry counts iff its composite
+ *   >= T64 (the Philox key for native rand-k; thresh == 0 keeps all; slack entries are listed
+ *   but sit below T64 and do not count), dropout-unbiased values are fl32(fl64(v) / p).
+ * gram[i*m + j] = sum_t (double)d_i[t] * (double)d_j[t]: every product exact (two float32
+ *   multiply exactly in float64), summed in float64.  gram: DEVICE float64[m*m], row-major,
+ *   16-B aligned.
+ * Non-finite rule: a client whose d_i holds a non-finite element (a kept NaN or +-inf, an
+ *   overflowing 1/p scaling, the all-NaN row of dropout-unbiased with p == 0) gets
+ *   gram[i][*] = gram[*][i] = NaN, the diagonal included; every other client is unaffected.
+ * gram is symmetric bit for bit (one triangle is computed and mirrored).
+ * Determinism: the order of summation is a function of the packets, n and m alone (not of the
+ *   device, its CU count or timing): the grid and each workgroup's chunk range come from n and
+ *   m, partial Grams go to the workspace and a second launch adds them in workgroup order.  No
+ *   floating-point atomics, no workgroup waits for another (no fc_fused_order_* handling).  Two
+ *   calls on the same packets give the same bits.
+ * Stream-ordered; no allocation, no host synchronisation.  ws: fc_gram_workspace_bytes(n, m)
+ *   bytes (monotone in n and m), 16-B aligned; it needs NO one-time zeroing: every word the call
+ *   reads it has written first.
+ * Argument errors return before the GPU is touched: FC_ERR_ARG for a NULL views_dev, gram or
+ *   ws, m < 1 or m > FC_GRAM_MAX_M, n == 0 (or n >= 2^32), a gram or ws that is not 16-B
+ *   aligned; FC_ERR_WORKSPACE for a short workspace. */
+#define FC_GRAM_MAX_M 128
+size_t fc_gram_workspace_bytes(uint64_t n, int m);
+int fc_packets_gram(const fc_packet_view* views_dev, int m, uint64_t n,
+                    double* gram /* DEVICE float64[m*m], row-major, 16-B aligned */,
+                    void* ws, size_t ws_bytes, fc_stream_t stream);
+
 /* ---- FedAVG over dense rows (gar.py:44 for 'full'): rows = DEVICE array of m row
  * pointers, w = DEVICE fp32[m]. */
 int fc_weighted_sum_dense(const float* const* rows, const float* w, int m, uint64_t n,

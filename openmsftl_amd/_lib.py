@@ -21,6 +21,7 @@ FC_KEY_MAGNITUDE, FC_KEY_PHILOX = 0, 1
 FC_FMT_IDXVAL, FC_FMT_BITMAP, FC_FMT_QSGD, FC_FMT_DENSE = 0, 1, 2, 3
 FC_PART_SAMPLE, FC_PART_FINISH = 1, 2
 FC_CHUNK = 8192
+FC_GRAM_MAX_M = 128
 HDR_BYTES = 96
 
 
@@ -108,6 +109,8 @@ SIGNATURES = {
     "fc_decode_dense": (_i32, [ctypes.POINTER(PacketView), _i32, _u64, _vp, _i32, _vp]),
     "fc_decode_accumulate": (_i32, [_vp, _i32, _i32, _u64, _vp, _vp]),
     "fc_decode_accumulate_continue": (_i32, [_vp, _i32, _i32, _u64, _vp, _vp]),
+    "fc_gram_workspace_bytes": (_sz, [_u64, _i32]),
+    "fc_packets_gram": (_i32, [_vp, _i32, _u64, _vp, _vp, _sz, _vp]),
     "fc_weighted_sum_dense": (_i32, [_vp, _vp, _i32, _u64, _vp, _vp]),
     "fc_weighted_sum_dense_continue": (_i32, [_vp, _vp, _i32, _u64, _vp, _vp]),
     "fc_div_scalar": (_i32, [_vp, _u64, ctypes.c_float, _vp]),

@@ -31,6 +31,19 @@ GAR (gar.py:44).  Here the rows never become a dense matrix on the common path:
   :func:`ef_batch_fold`): groups of <= 64 clients encoded by one fc_topk_encode_ef_batch launch
   chain and folded in row order, the same bits as the generic path.
 
+* ``aggregation_scheme: "krum"`` (gar.Krum) and ``aggregation_config["pc_analysis"] = "gram"``
+  take the "gram" route (:func:`gram_route_k`, :func:`gram_round`): the whole round's 'top'
+  packets resident at once (upload, one batched encode, resolve), their M x M float64 Gram matrix
+  straight from the packets (``codec.gram``), then the FedAVG fold (the "stream" route's bits:
+  the same encode, the same row-order fold) or Krum's selection.  With ``pc_analysis: "gram"``
+  the singular values of G, ``sqrt(max(eigvalsh(gram), 0))`` descending (float64, length M,
+  all NaN when the Gram holds NaN), are appended to ``self.gar.Sigma_tracked`` after the
+  round.  Unlike the reference's ``randomized_svd`` this draws nothing from ``np.random``, so
+  the global RNG stream of a run differs from the reference's by exactly those draws.  The
+  string is deliberate: ``pc_analysis: True`` keeps raising on the device class as before.  A
+  round that does not meet the route's conditions raises ``NotImplementedError`` naming the
+  condition (no silent dense fallback).
+
 ``aggregate_grads`` is a plain function so that :func:`openmsftl_amd.integration.install` can
 bind it onto the REFERENCE ``Aggregator`` class (its ``self.gar`` may then be a reference GAR
 with no ``aggregate_packets``: G is then handed over as the host array the reference builds).
@@ -51,7 +64,7 @@ import torch
 from . import _lib as L
 from . import codec
 from .compression import Compression, bitmask_words, kept_count
-from .gar import FedAvg
+from .gar import FedAvg, Krum, gram_singular_values
 from .pipeline import HostFedAvg, MtRedraw, RowCodec, RowPlan
 
 
@@ -472,6 +485,103 @@ def ef_batch_fold(agg, clients, n: int, k: int, weights: np.ndarray, dev: torch.
     return acc
 
 
+def gram_wanted(agg) -> bool:
+    """Does this round take the "gram" route: the device Krum, or the device FedAvg with
+    ``pc_analysis: "gram"`` (a patched reference class keeps its own routing)."""
+    gar = getattr(agg, "gar", None)
+    if type(gar) is Krum:
+        return True
+    pc = getattr(agg, "analyze_pc", False)
+    return isinstance(pc, str) and pc == "gram" and type(gar) is FedAvg
+
+
+def gram_resident_bytes(n: int, m: int) -> int:
+    """Device bytes the "gram" route holds at once: m gradients and their packets, the batched
+    encoder's and the Gram kernel's workspaces, the aggregate and the Gram matrix."""
+    from .pipeline import packet_bytes
+    lib = L.load()
+    return (m * (4 * n + packet_bytes(n)) + int(lib.fc_workspace_bytes_batch(n, m))
+            + int(lib.fc_gram_workspace_bytes(n, m)) + 4 * n + 8 * m * m)
+
+
+def gram_route_k(agg, clients) -> int:
+    """k of the round's common 'top' codec when the round meets the "gram" route's conditions;
+    otherwise ``NotImplementedError`` naming the condition that fails.  Touches no GPU (the
+    budget is checked here only when ``device_budget_bytes`` is configured; :func:`gram_round`
+    checks the default budget against the free memory)."""
+    def no(why: str):
+        raise NotImplementedError(f"the gram route (krum / pc_analysis='gram') needs {why}")
+    cfg = getattr(agg, "aggregation_config", None) or {}
+    if type(agg.gar) not in (FedAvg, Krum):
+        no("the device FedAvg or Krum")
+    if agg.num_hierarchies != 0:
+        no("no hierarchies (num_hierarchies == 0)")
+    if cfg.get("devices", DEFAULT_DEVICES) not in (None, 1):
+        no("one device")
+    w = getattr(agg.gar, "gradient_weights", None)
+    if w is not None and np.asarray(w).dtype != np.float32:
+        no("float32 GAR weights")
+    if len(clients) > L.FC_GRAM_MAX_M:
+        no(f"at most {L.FC_GRAM_MAX_M} clients (got {len(clients)})")
+    n, fr = None, None
+    for c in clients:
+        C, g = c.C, np.asarray(c.grad)
+        if getattr(C, "compression_function", None) != "top":
+            no("every client to compress with 'top'")
+        if getattr(C, "error_feedback", False):
+            no("'top' without error feedback")
+        if g.ndim != 1 or g.dtype != np.float32:
+            no("1-D float32 gradients")
+        if n is not None and g.shape[0] != n:
+            no("gradients of one length")
+        f = C.fraction_coordinates
+        if not isinstance(f, (int, float, np.floating, np.integer)) or not np.isfinite(f):
+            no("a finite fraction_coordinates")
+        if fr is not None and f != fr:
+            no("one common fraction_coordinates")
+        n, fr = g.shape[0], f
+    k = kept_count(fr, n)
+    if not 0 < k < n:
+        no(f"0 < k < n (k={k}, n={n})")
+    b = cfg.get("device_budget_bytes")
+    if b and gram_resident_bytes(n, len(clients)) > int(b):
+        no(f"the round's packets to fit device_budget_bytes ({gram_resident_bytes(n, len(clients))}"
+           f" > {int(b)} bytes)")
+    return k
+
+
+def gram_round(agg, clients, n: int, k: int, dev: torch.device) -> torch.Tensor:
+    """One round on the "gram" route: upload, one batched 'top' encode, resolve, the packets'
+    Gram matrix, then the FedAVG fold in row order (the "stream" route's bits) or Krum's selected
+    row.  Appends G's singular values to ``gar.Sigma_tracked`` for ``pc_analysis: "gram"``."""
+    m = len(clients)
+    need = gram_resident_bytes(n, m)
+    if need > _budget(agg, dev):
+        raise NotImplementedError("the gram route (krum / pc_analysis='gram') needs the round's packets "
+                                  f"to fit device_budget_bytes ({need} > {_budget(agg, dev)} bytes)")
+    cache = agg.__dict__.setdefault("_gram_packets", {})
+    packets = cache.get((n, dev))
+    if packets is None or len(packets) < m:
+        cache.clear()
+        packets = cache[(n, dev)] = codec.Packet.alloc_batch(n, m, L.FC_FMT_IDXVAL, dev, k=k)
+    pk = packets[:m]
+    grads = [torch.from_numpy(np.ascontiguousarray(c.grad)).to(dev) for c in clients]
+    codec.encode_top_batch(grads, k, packets=pk, check=False)
+    codec.resolve(pk)
+    for p in pk:
+        p.release()
+    del grads
+    gram = codec.gram(pk)
+    if type(agg.gar) is Krum:
+        out = agg.gar.aggregate_packets(pk, gram=gram)
+    else:
+        w = agg.gar._weights(m, np.float32)                         # gar.py:37-42 (persisted)
+        out = codec.decode_accumulate(pk, [float(x) for x in w])
+    if getattr(agg, "analyze_pc", False) == "gram":
+        agg.gar.Sigma_tracked.append(gram_singular_values(gram.cpu().numpy()))
+    return out
+
+
 def aggregate_grads(self, clients: List, input_feature: np.ndarray = None,
                     val_loader=None) -> None:
     """aggregation.py:54-78 on the device: sets ``self.agg_grad`` (host array) and
@@ -483,11 +593,20 @@ def aggregate_grads(self, clients: List, input_feature: np.ndarray = None,
         if ref is not None:                 # patched reference class: its own SVD analysis
             return ref(self, clients, input_feature, val_loader)
         raise NotImplementedError("pc_analysis (randomized SVD of G) is outside the hot path")
+    # Krum / pc_analysis "gram": a round outside the route's conditions raises here, before a
+    # GPU is touched (no dense fallback)
+    k_gram = gram_route_k(self, clients) if gram_wanted(self) else None
     dev = _device_of(self)
     grad0 = np.asarray(clients[0].grad)
     n = grad0.shape[0]
     if any(np.asarray(c.grad).shape != (n,) for c in clients):
         raise ValueError("client gradients must share one length (aggregation.py:61)")
+    if k_gram is not None:
+        # the round's packets resident at once, their Gram matrix straight from them
+        self.agg_path = "gram"
+        self.curr_G = None
+        self.agg_grad = gram_round(self, clients, n, k_gram, dev).cpu().numpy()
+        return
     k_ef = ef_batch_k(self, clients)
     if k_ef is not None:
         # opt-in: a round of error-feedback 'top' clients, batched (dense-fold's bits)
@@ -583,7 +702,7 @@ class Aggregator:
         self.gar = self.__get_gar()
         self.curr_G = None
         self.agg_grad = None
-        self.agg_path = None                # "stream" | "dense-fold" | "dense" | "ef-batch": the last call's path
+        self.agg_path = None                # "stream" | "dense-fold" | "dense" | "ef-batch" | "gram": the last call's path
         self.agg_draws = None               # streamed np.random draws: "device-mt" | "device-perm" | "host" | None
         self.analyze_pc = self.aggregation_config.get("pc_analysis", False)
         self.num_hierarchies = self.aggregation_config.get("num_hierarchies", 0)
@@ -596,6 +715,8 @@ class Aggregator:
         scheme = self.aggregation_config["aggregation_scheme"]
         if scheme == "fed_avg":
             return FedAvg(aggregation_config=self.aggregation_config)
+        if scheme == "krum":
+            return Krum(aggregation_config=self.aggregation_config)
         if scheme == "fed_spectral_avg":
             raise NotImplementedError("SpectralFedAvg is outside the codec hot path (DESIGN.md §8)")
         raise NotImplementedError

@@ -6,6 +6,7 @@
     pkt = encode_mask(g, codec, p, ...)    # compression.py:47-60 / rand parity
     q   = decode(pkt)                      # the dense vector compress() returns
     agg = decode_accumulate(pkts, w)       # aggregation.py:61-63 + gar.py:44, bit-exact fp32
+    gm  = gram(pkts)                       # G @ G.T in float64 straight from the packets
 
 Packets live on the GPU in the slotted layout of include/fedcodec.h: chunk c (8192 elements)
 lists its entries, ascending, at ``[c*8192, c*8192 + cnt[c])`` of ``idx``/``val`` (or
@@ -819,6 +820,56 @@ def decode_accumulate(packets: Sequence[Packet], weights, out: Optional[torch.Te
     fn = lib.fc_decode_accumulate_continue if continue_sum else lib.fc_decode_accumulate
     L.check(fn(_vp(views), len(packets), fmt, n, _vp(out), _stream(dev)),
             "fc_decode_accumulate")
+    return out
+
+
+class GramWorkspace:
+    """Per-(device, stream) scratch of :func:`gram` (the partial Grams; needs no zeroing)."""
+
+    _cache: dict = {}
+
+    def __init__(self, nbytes: int, device: torch.device):
+        self.nbytes = nbytes
+        self.buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+    @classmethod
+    def get(cls, n: int, m: int, device: torch.device) -> "GramWorkspace":
+        need = int(L.load().fc_gram_workspace_bytes(n, m))
+        key = (device.index if device.index is not None else torch.cuda.current_device(),
+               torch.cuda.current_stream(device).cuda_stream)
+        ws = cls._cache.get(key)
+        if ws is None or ws.nbytes < need:
+            ws = cls(need, device)
+            cls._cache[key] = ws
+        return ws
+
+
+def gram(packets: Sequence[Packet], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The (m, m) float64 Gram matrix ``G @ G.T`` of the rows :func:`decode` would make of the
+    packets, computed straight from them (fc_packets_gram: exact products, float64 sums, a fixed
+    order; a client with a non-finite element gets a NaN row and column).  At most
+    ``FC_GRAM_MAX_M`` idx/val packets of one length."""
+    if not packets:
+        raise ValueError("no packets")
+    m, n, dev = len(packets), packets[0].n, packets[0].val.device
+    if m > L.FC_GRAM_MAX_M:
+        raise ValueError(f"gram takes at most {L.FC_GRAM_MAX_M} packets (got {m})")
+    for p in packets:
+        if p.n != n:
+            raise ValueError("packets must share n")
+        if p.fmt != L.FC_FMT_IDXVAL or p.idx is None or p.qoff is None:
+            raise ValueError("gram needs idx/val packets (FC_FMT_IDXVAL) with quarter offsets")
+    lib = L.load()
+    if out is None:
+        out = torch.empty((m, m), dtype=torch.float64, device=dev)
+    if (not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or out.device != dev
+            or tuple(out.shape) != (m, m) or not out.is_contiguous() or out.data_ptr() % 16):
+        raise ValueError("out must be a contiguous 16-byte aligned (m, m) float64 tensor on the "
+                         "packets' device")
+    ws = GramWorkspace.get(n, m, dev)
+    views = views_tensor(packets, [1.0] * m, dev)
+    L.check(lib.fc_packets_gram(_vp(views), m, n, _vp(out), _vp(ws.buf), ws.nbytes, _stream(dev)),
+            "fc_packets_gram")
     return out
 
 

@@ -1123,3 +1123,70 @@ int fc_div_scalar_f64(double* x, uint64_t n, double d, fc_stream_t stream) {
 }
 
 }  // extern "C"
+
+// ---- packet Gram matrix (fc_gram.hip) -------------------------------------------------------
+// Geometry from n and m alone: tiles of kGT clients, their count rounded up to a power of two
+// p2; about kGSlices / p2 chunk slices, so tiles x slices fills the chip for any m.  A part is
+// an (8 p2) x (8 p2) float64 matrix per slice, then one flag word per (slice, client).
+namespace {
+struct GramGeom { uint32_t nch, mp, cps, slices; size_t part_bytes, bytes; };
+GramGeom gram_geom(uint64_t n, int m) {
+  GramGeom g;
+  const uint32_t tiles = ((uint32_t)m + kGT - 1) / kGT;
+  uint32_t p2 = 1;
+  while (p2 < tiles) p2 <<= 1;
+  g.nch = num_chunks(n);
+  g.mp = p2 * kGT;
+  const uint32_t cap = std::min<uint32_t>(g.nch, kGSlices / p2);   // slices the workspace holds
+  g.cps = (g.nch + cap - 1) / cap;
+  g.slices = (g.nch + g.cps - 1) / g.cps;                           // <= cap
+  g.part_bytes = (size_t)cap * g.mp * g.mp * sizeof(double);
+  g.bytes = g.part_bytes + (((size_t)cap * g.mp * sizeof(uint32_t) + 255) & ~(size_t)255);
+  return g;
+}
+int gram_lds_setup() {
+  static int rc = [] {
+    return hipFuncSetAttribute((const void*)k_gram, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)kGLdsBytes) == hipSuccess ? 0 : -1;
+  }();
+  return rc;
+}
+}  // namespace
+
+extern "C" {
+
+size_t fc_gram_workspace_bytes(uint64_t n, int m) {
+  if (n == 0 || n > 0xffffffffull || m < 1 || m > FC_GRAM_MAX_M) return 0;
+  return gram_geom(n, m).bytes;
+}
+
+int fc_packets_gram(const fc_packet_view* views_dev, int m, uint64_t n, double* gram, void* ws,
+                    size_t ws_bytes, fc_stream_t stream) {
+  static_assert(FC_GRAM_MAX_M == kGMaxM, "FC_GRAM_MAX_M");
+  FC_CHECK(views_dev != nullptr, "views_dev is NULL");
+  FC_CHECK(gram != nullptr, "gram is NULL");
+  FC_CHECK(ws != nullptr, "workspace is NULL");
+  FC_CHECK(m >= 1 && m <= FC_GRAM_MAX_M, "m=%d outside [1, %d]", m, FC_GRAM_MAX_M);
+  FC_CHECK(n >= 1 && n <= 0xffffffffull, "n=%llu outside [1, 2^32-1]", (unsigned long long)n);
+  FC_CHECK(((uintptr_t)gram & 15) == 0, "gram must be 16-byte aligned");
+  FC_CHECK(((uintptr_t)ws & 15) == 0, "workspace must be 16-byte aligned");
+  const GramGeom g = gram_geom(n, m);
+  if (ws_bytes < g.bytes)
+    return fail(FC_ERR_WORKSPACE, "workspace %zu B < %zu B needed", ws_bytes, g.bytes);
+  if (gram_lds_setup() != 0) return fail(FC_ERR_HIP, "k_gram: cannot reserve %zu B of LDS", kGLdsBytes);
+  GramArgs a;
+  memset(&a, 0, sizeof a);
+  a.views = views_dev; a.gram = gram; a.n = n; a.m = (uint32_t)m; a.mp = g.mp;
+  a.part = reinterpret_cast<double*>(ws);
+  a.bad = reinterpret_cast<uint32_t*>(static_cast<char*>(ws) + g.part_bytes);
+  a.nch = g.nch; a.cps = g.cps; a.slices = g.slices;
+  hipStream_t s = (hipStream_t)stream;
+  const uint32_t tiles = ((uint32_t)m + kGT - 1) / kGT;
+  hipLaunchKernelGGL(k_gram, dim3(tiles, g.slices), dim3(kGBlock), kGLdsBytes, s, a);
+  FC_LAUNCHED("k_gram");
+  hipLaunchKernelGGL(k_gram_fin, dim3(((uint32_t)(m * m) + kBlock - 1) / kBlock), dim3(kBlock), 0, s, a);
+  FC_LAUNCHED("k_gram_fin");
+  return FC_OK;
+}
+
+}  // extern "C"
