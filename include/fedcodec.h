@@ -326,6 +326,39 @@ int fc_packets_gram(const fc_packet_view* views_dev, int m, uint64_t n,
                     double* gram /* DEVICE float64[m*m], row-major, 16-B aligned */,
                     void* ws, size_t ws_bytes, fc_stream_t stream);
 
+/* ---- A round's packets times a dense vector: G v in float64 without the dense G -----------
+ * What a rule that is linear in the rows of G needs beside the Gram matrix (aggregate =
+ * a v + sum_i c_i d_i with a carried vector v: b = G v and |v|^2; with v = ones the row sums
+ * of the reference's explained-variance ratio, spectral_aggregation.py:100-103), computed
+ * straight from the packets (fc_dot.hip).
+ * views_dev: DEVICE array of m FC_FMT_IDXVAL views with qoff present, as fc_packets_gram takes
+ *   them; `weight` is ignored.  1 <= m <= FC_GRAM_MAX_M.
+ * d_i: exactly the row fc_packets_gram uses (the same kept-entry rule: composite >= T64, the
+ *   Philox key for native rand-k, thresh == 0 keeps all, slack entries do not count;
+ *   dropout-unbiased values are fl32(fl64(v) / p)).
+ * v: DEVICE float32[n], 16-B aligned, or NULL for the all-ones vector.
+ * out: DEVICE float64[m + 1], 16-B aligned.  out[i] = sum_t (double)d_i[t] * (double)v[t] for
+ *   i < m (v[t] = 1 when v is NULL: the row sum); out[m] = sum_t (double)v[t]^2 (exactly
+ *   (double)n when v is NULL).  Every product is exact, sums are float64 and start from +0.0.
+ * Non-finite rule: a client whose d_i holds a non-finite element (a kept NaN or +-inf, an
+ *   overflowing 1/p scaling, dropout-unbiased with p == 0) gets out[i] = NaN, the clients the
+ *   Gram's rule marks; every other client is unaffected.  If v holds a non-finite element all
+ *   m + 1 outputs are NaN.
+ * Determinism: the order of summation is a function of the packets, n and m alone: the grid and
+ *   each workgroup's chunk range come from n and m, partial sums go to the workspace and a second
+ *   launch adds them in a fixed order.  No floating-point atomics, no workgroup waits for
+ *   another.  Two calls on the same inputs give the same bits.
+ * Stream-ordered; no allocation, no host synchronisation.  ws: fc_dot_workspace_bytes(n, m)
+ *   bytes (monotone in n and m), 16-B aligned; it needs NO one-time zeroing.
+ * Argument errors return before the GPU is touched: FC_ERR_ARG for a NULL views_dev, out or ws,
+ *   m < 1 or m > FC_GRAM_MAX_M, n == 0 (or n >= 2^32), a v, out or ws that is not 16-B aligned;
+ *   FC_ERR_WORKSPACE for a short workspace. */
+size_t fc_dot_workspace_bytes(uint64_t n, int m);
+int fc_packets_dot(const fc_packet_view* views_dev, int m, uint64_t n,
+                   const float* v /* DEVICE float32[n], 16-B aligned, or NULL = all ones */,
+                   double* out /* DEVICE float64[m + 1], 16-B aligned */,
+                   void* ws, size_t ws_bytes, fc_stream_t stream);
+
 /* ---- FedAVG over dense rows (gar.py:44 for 'full'): rows = DEVICE array of m row
  * pointers, w = DEVICE fp32[m]. */
 int fc_weighted_sum_dense(const float* const* rows, const float* w, int m, uint64_t n,

@@ -111,6 +111,8 @@ SIGNATURES = {
     "fc_decode_accumulate_continue": (_i32, [_vp, _i32, _i32, _u64, _vp, _vp]),
     "fc_gram_workspace_bytes": (_sz, [_u64, _i32]),
     "fc_packets_gram": (_i32, [_vp, _i32, _u64, _vp, _vp, _sz, _vp]),
+    "fc_dot_workspace_bytes": (_sz, [_u64, _i32]),
+    "fc_packets_dot": (_i32, [_vp, _i32, _u64, _vp, _vp, _vp, _sz, _vp]),
     "fc_weighted_sum_dense": (_i32, [_vp, _vp, _i32, _u64, _vp, _vp]),
     "fc_weighted_sum_dense_continue": (_i32, [_vp, _vp, _i32, _u64, _vp, _vp]),
     "fc_div_scalar": (_i32, [_vp, _u64, ctypes.c_float, _vp]),

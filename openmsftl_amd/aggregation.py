@@ -43,6 +43,11 @@ GAR (gar.py:44).  Here the rows never become a dense matrix on the common path:
   string is deliberate: ``pc_analysis: True`` keeps raising on the device class as before.  A
   round that does not meet the route's conditions raises ``NotImplementedError`` naming the
   condition (no silent dense fallback).
+* ``aggregation_scheme: "spectral_gram"`` / ``"geometric_median"`` / ``"centered_clip"``
+  (gar.LinearRule) take the same route: coefficients from the Gram matrix (and
+  ``codec.dot_dense`` for row sums or a carried vector), then the row-order fold of the packets
+  with those coefficients.  ``"fed_spectral_avg"`` (the reference's class, with its autoencoder
+  branch) keeps raising.
 
 ``aggregate_grads`` is a plain function so that :func:`openmsftl_amd.integration.install` can
 bind it onto the REFERENCE ``Aggregator`` class (its ``self.gar`` may then be a reference GAR
@@ -64,7 +69,8 @@ import torch
 from . import _lib as L
 from . import codec
 from .compression import Compression, bitmask_words, kept_count
-from .gar import FedAvg, Krum, gram_singular_values
+from .gar import (CenteredClip, FedAvg, GeometricMedian, Krum, LinearRule, SpectralGram,
+                  gram_singular_values)
 from .pipeline import HostFedAvg, MtRedraw, RowCodec, RowPlan
 
 
@@ -485,11 +491,16 @@ def ef_batch_fold(agg, clients, n: int, k: int, weights: np.ndarray, dev: torch.
     return acc
 
 
+#: the rules that are linear in the rows of G (gar.LinearRule): the "gram" route's other GARs
+_LINEAR_RULES = (SpectralGram, GeometricMedian, CenteredClip)
+
+
 def gram_wanted(agg) -> bool:
-    """Does this round take the "gram" route: the device Krum, or the device FedAvg with
+    """Does this round take the "gram" route: the device Krum, a linear rule (spectral_gram,
+    geometric_median, centered_clip), or the device FedAvg with
     ``pc_analysis: "gram"`` (a patched reference class keeps its own routing)."""
     gar = getattr(agg, "gar", None)
-    if type(gar) is Krum:
+    if type(gar) in (Krum,) + _LINEAR_RULES:
         return True
     pc = getattr(agg, "analyze_pc", False)
     return isinstance(pc, str) and pc == "gram" and type(gar) is FedAvg
@@ -497,11 +508,13 @@ def gram_wanted(agg) -> bool:
 
 def gram_resident_bytes(n: int, m: int) -> int:
     """Device bytes the "gram" route holds at once: m gradients and their packets, the batched
-    encoder's and the Gram kernel's workspaces, the aggregate and the Gram matrix."""
+    encoder's, the Gram kernel's and the dot kernel's workspaces, the aggregate, a carried
+    vector (centered_clip) and the Gram matrix."""
     from .pipeline import packet_bytes
     lib = L.load()
     return (m * (4 * n + packet_bytes(n)) + int(lib.fc_workspace_bytes_batch(n, m))
-            + int(lib.fc_gram_workspace_bytes(n, m)) + 4 * n + 8 * m * m)
+            + int(lib.fc_gram_workspace_bytes(n, m)) + int(lib.fc_dot_workspace_bytes(n, m))
+            + 4 * n + 4 * n + 8 * m * m)
 
 
 def gram_route_k(agg, clients) -> int:
@@ -512,8 +525,8 @@ def gram_route_k(agg, clients) -> int:
     def no(why: str):
         raise NotImplementedError(f"the gram route (krum / pc_analysis='gram') needs {why}")
     cfg = getattr(agg, "aggregation_config", None) or {}
-    if type(agg.gar) not in (FedAvg, Krum):
-        no("the device FedAvg or Krum")
+    if type(agg.gar) not in (FedAvg, Krum) + _LINEAR_RULES:
+        no("the device FedAvg or Krum (or spectral_gram / geometric_median / centered_clip)")
     if agg.num_hierarchies != 0:
         no("no hierarchies (num_hierarchies == 0)")
     if cfg.get("devices", DEFAULT_DEVICES) not in (None, 1):
@@ -552,8 +565,9 @@ def gram_route_k(agg, clients) -> int:
 
 def gram_round(agg, clients, n: int, k: int, dev: torch.device) -> torch.Tensor:
     """One round on the "gram" route: upload, one batched 'top' encode, resolve, the packets'
-    Gram matrix, then the FedAVG fold in row order (the "stream" route's bits) or Krum's selected
-    row.  Appends G's singular values to ``gar.Sigma_tracked`` for ``pc_analysis: "gram"``."""
+    Gram matrix, then the FedAVG fold in row order (the "stream" route's bits), Krum's selected
+    row or a linear rule's fold.  Appends G's singular values to ``gar.Sigma_tracked`` for
+    ``pc_analysis: "gram"`` (after the entry ``SpectralGram`` appends itself: two per round)."""
     m = len(clients)
     need = gram_resident_bytes(n, m)
     if need > _budget(agg, dev):
@@ -572,7 +586,7 @@ def gram_round(agg, clients, n: int, k: int, dev: torch.device) -> torch.Tensor:
         p.release()
     del grads
     gram = codec.gram(pk)
-    if type(agg.gar) is Krum:
+    if isinstance(agg.gar, (Krum, LinearRule)):
         out = agg.gar.aggregate_packets(pk, gram=gram)
     else:
         w = agg.gar._weights(m, np.float32)                         # gar.py:37-42 (persisted)
@@ -717,6 +731,12 @@ class Aggregator:
             return FedAvg(aggregation_config=self.aggregation_config)
         if scheme == "krum":
             return Krum(aggregation_config=self.aggregation_config)
+        if scheme == "spectral_gram":
+            return SpectralGram(aggregation_config=self.aggregation_config)
+        if scheme == "geometric_median":
+            return GeometricMedian(aggregation_config=self.aggregation_config)
+        if scheme == "centered_clip":
+            return CenteredClip(aggregation_config=self.aggregation_config)
         if scheme == "fed_spectral_avg":
             raise NotImplementedError("SpectralFedAvg is outside the codec hot path (DESIGN.md §8)")
         raise NotImplementedError

@@ -7,6 +7,7 @@
     q   = decode(pkt)                      # the dense vector compress() returns
     agg = decode_accumulate(pkts, w)       # aggregation.py:61-63 + gar.py:44, bit-exact fp32
     gm  = gram(pkts)                       # G @ G.T in float64 straight from the packets
+    b   = dot_dense(pkts, v)               # [G @ v, v @ v] in float64 (v=None: row sums, n)
 
 Packets live on the GPU in the slotted layout of include/fedcodec.h: chunk c (8192 elements)
 lists its entries, ascending, at ``[c*8192, c*8192 + cnt[c])`` of ``idx``/``val`` (or
@@ -870,6 +871,64 @@ def gram(packets: Sequence[Packet], out: Optional[torch.Tensor] = None) -> torch
     views = views_tensor(packets, [1.0] * m, dev)
     L.check(lib.fc_packets_gram(_vp(views), m, n, _vp(out), _vp(ws.buf), ws.nbytes, _stream(dev)),
             "fc_packets_gram")
+    return out
+
+
+class DotWorkspace:
+    """Per-(device, stream) scratch of :func:`dot_dense` (the partial sums; needs no zeroing)."""
+
+    _cache: dict = {}
+
+    def __init__(self, nbytes: int, device: torch.device):
+        self.nbytes = nbytes
+        self.buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+    @classmethod
+    def get(cls, n: int, m: int, device: torch.device) -> "DotWorkspace":
+        need = int(L.load().fc_dot_workspace_bytes(n, m))
+        key = (device.index if device.index is not None else torch.cuda.current_device(),
+               torch.cuda.current_stream(device).cuda_stream)
+        ws = cls._cache.get(key)
+        if ws is None or ws.nbytes < need:
+            ws = cls(need, device)
+            cls._cache[key] = ws
+        return ws
+
+
+def dot_dense(packets: Sequence[Packet], v: Optional[torch.Tensor] = None,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The (m + 1,) float64 tensor ``[G @ v, v @ v]`` of the rows :func:`decode` would make of the
+    packets (the rows :func:`gram` uses) and a dense float32 device vector ``v``, computed
+    straight from the packets (fc_packets_dot: exact products, float64 sums, a fixed order).
+    ``v=None`` is the all-ones vector: the row sums, then ``float(n)``.  A client with a
+    non-finite element gets NaN; a non-finite ``v`` makes every output NaN.  At most
+    ``FC_GRAM_MAX_M`` idx/val packets of one length."""
+    if not packets:
+        raise ValueError("no packets")
+    m, n, dev = len(packets), packets[0].n, packets[0].val.device
+    if m > L.FC_GRAM_MAX_M:
+        raise ValueError(f"gram takes at most {L.FC_GRAM_MAX_M} packets (got {m})")
+    for p in packets:
+        if p.n != n:
+            raise ValueError("packets must share n")
+        if p.fmt != L.FC_FMT_IDXVAL or p.idx is None or p.qoff is None:
+            raise ValueError("gram needs idx/val packets (FC_FMT_IDXVAL) with quarter offsets")
+    if v is not None:
+        if (not isinstance(v, torch.Tensor) or v.dtype != torch.float32 or v.device != dev
+                or v.numel() != n or not v.is_contiguous() or v.data_ptr() % 16):
+            raise ValueError("v must be a contiguous 16-byte aligned float32 tensor of n elements "
+                             "on the packets' device")
+    lib = L.load()
+    if out is None:
+        out = torch.empty(m + 1, dtype=torch.float64, device=dev)
+    if (not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or out.device != dev
+            or tuple(out.shape) != (m + 1,) or not out.is_contiguous() or out.data_ptr() % 16):
+        raise ValueError("out must be a contiguous 16-byte aligned (m + 1,) float64 tensor on the "
+                         "packets' device")
+    ws = DotWorkspace.get(n, m, dev)
+    views = views_tensor(packets, [1.0] * m, dev)
+    L.check(lib.fc_packets_dot(_vp(views), m, n, _vp(v), _vp(out), _vp(ws.buf), ws.nbytes,
+                               _stream(dev)), "fc_packets_dot")
     return out
 
 

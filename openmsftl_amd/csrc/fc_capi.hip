@@ -1190,3 +1190,61 @@ int fc_packets_gram(const fc_packet_view* views_dev, int m, uint64_t n, double* 
 }
 
 }  // extern "C"
+
+// ---- packets times a dense vector (fc_dot.hip) ------------------------------------------------
+// Geometry from n and m alone: tiles of kVTile clients, about kVSlices / tiles chunk slices.  The
+// workspace is laid out for kVSlices slices of kGMaxM clients whatever m is (monotone in m and
+// n): per-client partial sums, the partial sums of v's squares, then the flags.
+namespace {
+struct DotGeom { uint32_t nch, tiles, cps, slices; size_t part_bytes, q_bytes, bytes; };
+DotGeom dot_geom(uint64_t n, int m) {
+  DotGeom g;
+  g.nch = num_chunks(n);
+  g.tiles = ((uint32_t)m + kVTile - 1) / kVTile;
+  const uint32_t cap = std::min<uint32_t>(g.nch, kVSlices / g.tiles);
+  g.cps = (g.nch + cap - 1) / cap;
+  g.slices = (g.nch + g.cps - 1) / g.cps;                           // <= cap
+  const size_t rows = std::min<uint32_t>(g.nch, kVSlices);          // slices the workspace holds
+  g.part_bytes = rows * kVStride * sizeof(double);
+  g.q_bytes = (rows * sizeof(double) + 255) & ~(size_t)255;
+  g.bytes = g.part_bytes + g.q_bytes + ((rows * kVStride * sizeof(uint32_t) + 255) & ~(size_t)255);
+  return g;
+}
+}  // namespace
+
+extern "C" {
+
+size_t fc_dot_workspace_bytes(uint64_t n, int m) {
+  if (n == 0 || n > 0xffffffffull || m < 1 || m > FC_GRAM_MAX_M) return 0;
+  return dot_geom(n, m).bytes;
+}
+
+int fc_packets_dot(const fc_packet_view* views_dev, int m, uint64_t n, const float* v, double* out,
+                   void* ws, size_t ws_bytes, fc_stream_t stream) {
+  FC_CHECK(views_dev != nullptr, "views_dev is NULL");
+  FC_CHECK(out != nullptr, "out is NULL");
+  FC_CHECK(ws != nullptr, "workspace is NULL");
+  FC_CHECK(m >= 1 && m <= FC_GRAM_MAX_M, "m=%d outside [1, %d]", m, FC_GRAM_MAX_M);
+  FC_CHECK(n >= 1 && n <= 0xffffffffull, "n=%llu outside [1, 2^32-1]", (unsigned long long)n);
+  FC_CHECK(((uintptr_t)v & 15) == 0, "v must be 16-byte aligned");
+  FC_CHECK(((uintptr_t)out & 15) == 0, "out must be 16-byte aligned");
+  FC_CHECK(((uintptr_t)ws & 15) == 0, "workspace must be 16-byte aligned");
+  const DotGeom g = dot_geom(n, m);
+  if (ws_bytes < g.bytes)
+    return fail(FC_ERR_WORKSPACE, "workspace %zu B < %zu B needed", ws_bytes, g.bytes);
+  DotArgs a;
+  memset(&a, 0, sizeof a);
+  a.views = views_dev; a.v = v; a.out = out; a.n = n; a.m = (uint32_t)m;
+  a.part = reinterpret_cast<double*>(ws);
+  a.qpart = reinterpret_cast<double*>(static_cast<char*>(ws) + g.part_bytes);
+  a.bad = reinterpret_cast<uint32_t*>(static_cast<char*>(ws) + g.part_bytes + g.q_bytes);
+  a.nch = g.nch; a.cps = g.cps; a.slices = g.slices;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_dot, dim3(g.tiles, g.slices), dim3(kVBlock), 0, s, a);
+  FC_LAUNCHED("k_dot");
+  hipLaunchKernelGGL(k_dot_fin, dim3((uint32_t)m + 1), dim3(64), 0, s, a);
+  FC_LAUNCHED("k_dot_fin");
+  return FC_OK;
+}
+
+}  // extern "C"

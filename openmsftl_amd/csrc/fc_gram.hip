@@ -69,6 +69,20 @@ struct GramArgs {
   uint32_t nch, cps, slices;                      // chunks; chunks per slice; slices launched
 };
 
+// One packet's GramMeta from its view (reads the packet's device header).
+__device__ __forceinline__ GramMeta gram_meta(const fc_packet_view& v) {
+  const fc_packet_hdr* h = v.hdr;
+  GramMeta d;
+  d.idx = v.idx; d.val = v.val; d.qoff = v.qoff; d.hdr = h; d.thresh = h->thresh; d.pad_ = 0;
+  const uint32_t ib = h->index_bits & 0xffu, codec = h->codec, key_mode = h->key_mode;
+  const bool unb = codec == FC_CODEC_DROPOUT_UNBIASED;
+  const bool generic = unb || (key_mode == FC_KEY_PHILOX && d.thresh != 0) ||
+                       (d.thresh >> ib) >= 0x7f800000ull;
+  d.flags = ib | ((codec & 0xffu) << 8) | ((key_mode & 0xffu) << 16) |
+            (generic ? kGGeneric : 0u) | ((unb && h->p == 0.0) ? kGDead : 0u);
+  return d;
+}
+
 // The per-(client, chunk) constants of the keep rule (wave-uniform).
 struct GramRule {
   PktCache pk;                                    // generic: entry_kept + fl32(fl64(v)/p)
@@ -175,17 +189,7 @@ __global__ __launch_bounds__(kGBlock, 1) void k_gram(GramArgs a) {
   for (int i = tid; i < kGT * kGMaxM; i += kGBlock) blk[i] = 0.0;
   if (tid == 0) *sbad = 0u;
   if ((uint32_t)tid < M) {
-    const fc_packet_view v = a.views[tid];
-    const fc_packet_hdr* h = v.hdr;
-    GramMeta d;
-    d.idx = v.idx; d.val = v.val; d.qoff = v.qoff; d.hdr = h; d.thresh = h->thresh; d.pad_ = 0;
-    const uint32_t ib = h->index_bits & 0xffu, codec = h->codec, key_mode = h->key_mode;
-    const bool unb = codec == FC_CODEC_DROPOUT_UNBIASED;
-    const bool generic = unb || (key_mode == FC_KEY_PHILOX && d.thresh != 0) ||
-                         (d.thresh >> ib) >= 0x7f800000ull;
-    d.flags = ib | ((codec & 0xffu) << 8) | ((key_mode & 0xffu) << 16) |
-              (generic ? kGGeneric : 0u) | ((unb && h->p == 0.0) ? kGDead : 0u);
-    meta[tid] = d;
+    meta[tid] = gram_meta(a.views[tid]);
   }
   __syncthreads();
 

@@ -6,6 +6,7 @@
 #include "fc_qsgd.hip"
 #include "fc_f64.hip"
 #include "fc_gram.hip"
+#include "fc_dot.hip"
 #include "fc_capi.hip"
 #include "fc_ef.hip"
 #include "fc_mt.hip"

@@ -18,6 +18,16 @@ takes float32 weights (float64 weights go through the dense path of the Aggregat
 ``Krum`` selects one client from the clients' geometry, which it reads from the M x M Gram
 matrix alone (``codec.gram`` for packets, a float64 torch product for a dense G);
 ``gram_singular_values`` gives G's singular values from the same matrix.
+
+``LinearRule`` is the base of the robust rules whose aggregate is linear in the rows of G,
+``a * v + sum_i c_i * d_i`` (``v`` an optional dense vector the server carries): the coefficients
+come from the Gram matrix ``K = G G^T``, ``b = G v`` and ``|v|^2`` alone (``codec.gram``,
+``codec.dot_dense``), through three pure NumPy float64 functions (``spectral_coeffs``,
+``geometric_median_coeffs``, ``centered_clip_coeffs``), and the sum is the library's row-order
+float32 fold (``codec.decode_accumulate``).  ``SpectralGram`` is the analytic branch of the
+reference's ``SpectralFedAvg`` (gar.py:123-134, ``fast_lr_decomposition``) restated on the
+Gram, ``GeometricMedian`` the smoothed Weiszfeld iteration (RFA), ``CenteredClip`` centered
+clipping (Karimireddy, He, Jaggi, ICML 2021).
 """
 from __future__ import annotations
 
@@ -164,3 +174,239 @@ class Krum(GAR):
         G64 = Gd.double()
         sel = self._pick((G64 @ G64.T).cpu().numpy())
         return G[sel]
+
+
+# ---- rules that are linear in the rows of G: coefficients from the Gram matrix ---------------
+def _check_th(adaptive_rank_th) -> None:
+    if adaptive_rank_th and not 0 < adaptive_rank_th < 1:      # spectral_aggregation.py:97-99
+        raise ValueError("adaptive_rank_th should be between 0 and 1")
+
+
+def spectral_coeffs(K, w, n: int, rank=None, adaptive_rank_th=None, drop_top_comp: bool = False,
+                    row_sums=None):
+    """``(c, S)`` with ``c @ G`` the reference's ``weighted_average(fast_lr_decomposition(G))``
+    (gar.py:123-134, spectral_aggregation.py:87-130) for the M x n matrix G whose Gram matrix is
+    ``K``: the low-rank approximation is ``V_k^T V_k G`` with the rows of ``V`` the eigenvectors of
+    K (descending), so the weighted average is ``(V_k^T V_k w) @ G``.  ``S`` are the ``rank``
+    leading singular values, ``sqrt(max(eigenvalue, 0))``.  ``row_sums`` (the sums of G's rows) is
+    needed with a truthy ``adaptive_rank_th`` only: the reference's total variance is
+    ``sum_i (K_ii - s_i^2 / n) / (n - 1)``.  Exact eigenvectors instead of the reference's
+    randomized SVD: draws nothing from ``np.random``.  Pure NumPy float64."""
+    K = np.asarray(K, dtype=np.float64)
+    w = np.asarray(w, dtype=np.float64)
+    M = K.shape[0]
+    if not rank or rank > min(M, n):
+        rank = min(M, n)
+    _check_th(adaptive_rank_th)
+    lam, Q = np.linalg.eigh(K)
+    lam, V = lam[::-1], Q[:, ::-1].T
+    S = np.sqrt(np.maximum(lam, 0.0))[:rank].copy()
+    V_k = V[:rank]
+    if adaptive_rank_th:
+        if row_sums is None:
+            raise ValueError("adaptive_rank_th needs the row sums of G")
+        s = np.asarray(row_sums, dtype=np.float64)
+        total_var = float(np.sum((np.diagonal(K) - s * s / n) / (n - 1)))
+        cum = np.cumsum(S ** 2 / (n - 1) / total_var)
+        ar = int(np.searchsorted(cum, adaptive_rank_th))
+        if ar == 0:
+            if drop_top_comp:
+                ar += 1
+            ar += 1
+        V_k = V_k[0:ar]
+    if drop_top_comp:
+        V_k = V_k[1:]
+    return V_k.T @ (V_k @ w), S
+
+
+def geometric_median_coeffs(K, alpha, iters: int = 100, tol: float = 1e-12, nu: float = 1e-6):
+    """``(c, iterations)``: the smoothed Weiszfeld iteration for the ``alpha``-weighted geometric
+    median of G's rows (RFA: Pillutla, Kakade, Harchaoui), run on the coefficients of the
+    iterate ``z = c @ G``: ``|z - g_i|^2 = c.Kc - 2 (Kc)_i + K_ii``.  Starts from ``c = alpha``;
+    ``beta_i = alpha_i / max(nu * sqrt(max K_ii), dist_i)``, ``c = beta / sum(beta)``; stops after
+    ``iters`` updates or when the objective ``sum alpha_i dist_i`` decreased by less than ``tol``
+    relative.  Pure NumPy float64."""
+    K = np.asarray(K, dtype=np.float64)
+    alpha = np.asarray(alpha, dtype=np.float64)
+    d = np.diagonal(K)
+    top = float(np.max(d))
+    if top == 0.0:
+        return alpha.copy(), 0
+    nu_abs = nu * np.sqrt(top)
+    c, prev, done = alpha.copy(), None, 0
+    for _ in range(int(iters)):
+        Kc = K @ c
+        dist = np.sqrt(np.maximum(0.0, c @ Kc - 2.0 * Kc + d))
+        obj = float(alpha @ dist)
+        if prev is not None and prev - obj < tol * prev:
+            break
+        beta = alpha / np.maximum(nu_abs, dist)
+        c = beta / np.sum(beta)
+        prev, done = obj, done + 1
+    return c, done
+
+
+def centered_clip_coeffs(K, b, q: float, tau: float, iters: int = 3):
+    """``(a, c)`` with ``a * v + c @ G`` the result of ``iters`` centered-clipping steps from
+    ``v`` (Karimireddy, He, Jaggi, ICML 2021): ``z <- z + mean_i (g_i - z) min(1, tau / |g_i -
+    z|)``, run on the coefficients of ``z = a v + c @ G`` with ``b = G v`` and ``q = |v|^2``:
+    ``|g_i - z|^2 = K_ii - 2 (a b_i + (Kc)_i) + a^2 q + 2 a c.b + c.Kc``.  ``b=None`` is the zero
+    start (b = 0, q = 0).  Pure NumPy float64."""
+    K = np.asarray(K, dtype=np.float64)
+    M = K.shape[0]
+    b = np.zeros(M) if b is None else np.asarray(b, dtype=np.float64)
+    d = np.diagonal(K)
+    a, c = 1.0, np.zeros(M)
+    for _ in range(int(iters)):
+        Kc = K @ c
+        d2 = d - 2.0 * (a * b + Kc) + (a * a * q + 2.0 * a * (c @ b) + c @ Kc)
+        dist = np.sqrt(np.maximum(0.0, d2))
+        s = np.where(dist > tau, tau / np.where(dist > tau, dist, 1.0), 1.0)
+        S = float(np.sum(s))
+        a, c = a * (1.0 - S / M), c * (1.0 - S / M) + s / M
+    return a, c
+
+
+class LinearRule(GAR):
+    """A rule whose aggregate is ``carry * v + sum_i coeffs_i * d_i``.  ``aggregate_packets``
+    computes the Gram matrix (unless given) and, if the rule needs it, ``codec.dot_dense``; runs
+    the rule's pure coefficient function; stores ``coeffs`` (float64, length M), ``carry`` (0.0
+    when no vector is carried) and ``excluded``; then folds ``coeffs.astype(float32)`` over the
+    non-excluded packets in row order (``codec.decode_accumulate``), from +0 or from
+    ``torch.mul(v, float32(carry))``.  The aggregate is float32.
+
+    A client whose Gram diagonal is NaN (a non-finite element) is excluded: the rule runs on the
+    remaining sub-block, weights restricted (not renormalised), its coefficient is exactly 0
+    and its packet is not given to the fold."""
+
+    def __init__(self, aggregation_config):
+        GAR.__init__(self, aggregation_config=aggregation_config)
+        self.coeffs = None
+        self.carry = 0.0
+        self.excluded = []
+
+    def aggregate(self, G, client_ids=None):
+        raise NotImplementedError(f"{type(self).__name__} reads the clients' geometry from their "
+                                  "packets (aggregate_packets, the Aggregator's gram route); a "
+                                  "dense G is not taken")
+
+    def _coeffs(self, K, w, packets, keep, n):
+        """(coefficients of the kept clients, carry, carried vector or None)."""
+        raise NotImplementedError
+
+    def _after(self, agg: torch.Tensor) -> None:
+        pass
+
+    @staticmethod
+    def _dot(packets, keep, v=None):
+        """(b over the kept clients, |v|^2) from codec.dot_dense, both checked to be finite."""
+        r = codec.dot_dense(packets, v).cpu().numpy()
+        b, q = r[:len(packets)][keep], float(r[len(packets)])
+        if not (np.all(np.isfinite(b)) and np.isfinite(q)):
+            raise ValueError("the carried vector holds a non-finite element (G v is not finite)")
+        return b, q
+
+    def aggregate_packets(self, packets: Sequence["codec.Packet"], out=None,
+                          gram: Optional[torch.Tensor] = None) -> torch.Tensor:
+        M = len(packets)
+        w = self._weights(M, np.float32)
+        if w.dtype != np.float32:
+            raise TypeError("aggregate_packets folds with float32 weights")
+        if gram is None:
+            gram = codec.gram(packets)
+        K = gram.cpu().numpy()
+        bad = np.isnan(np.diagonal(K))
+        keep = np.nonzero(~bad)[0]
+        if keep.size == 0:
+            raise ValueError("every client holds a non-finite element: nothing to aggregate")
+        c_sub, a, v = self._coeffs(K[np.ix_(keep, keep)], w[keep], packets, keep, packets[0].n)
+        coeffs = np.zeros(M, dtype=np.float64)
+        coeffs[keep] = c_sub
+        self.coeffs, self.carry = coeffs, float(a)
+        self.excluded = [int(i) for i in np.nonzero(bad)[0]]
+        c32 = coeffs.astype(np.float32)
+        kept = [packets[i] for i in keep]
+        weights = [float(c32[i]) for i in keep]
+        if v is None:
+            agg = codec.decode_accumulate(kept, weights, out=out)
+        else:
+            a32 = float(np.float32(self.carry))
+            acc = torch.mul(v, a32) if out is None else torch.mul(v, a32, out=out)
+            agg = codec.decode_accumulate(kept, weights, out=acc, continue_sum=True)
+        self._after(agg)
+        return agg
+
+
+class SpectralGram(LinearRule):
+    """The analytic branch of the reference's ``SpectralFedAvg`` (``conventional_pca_aggregation``,
+    gar.py:123-134): the FedAVG of the rank-truncated G, from the Gram matrix
+    (:func:`spectral_coeffs`).  Config keys ``rank``, ``adaptive_rank_th`` (default -1 as in the
+    reference, which a truthy value outside (0, 1) makes raise), ``drop_top_comp``.  Appends the
+    singular values ``S[:rank]`` to ``Sigma_tracked``; under ``pc_analysis: "gram"`` the
+    Aggregator appends all M of the whole Gram after them, two entries per round.  Draws nothing
+    from ``np.random``."""
+
+    def __init__(self, aggregation_config):
+        LinearRule.__init__(self, aggregation_config=aggregation_config)
+        self.rank = aggregation_config.get("rank", None)
+        self.adaptive_rank_th = aggregation_config.get("adaptive_rank_th", -1)
+        self.drop_top_comp = aggregation_config.get("drop_top_comp", False)
+        _check_th(self.adaptive_rank_th)
+
+    def _coeffs(self, K, w, packets, keep, n):
+        s = self._dot(packets, keep)[0] if self.adaptive_rank_th else None
+        c, S = spectral_coeffs(K, w, n, rank=self.rank, adaptive_rank_th=self.adaptive_rank_th,
+                               drop_top_comp=self.drop_top_comp, row_sums=s)
+        self.Sigma_tracked.append(S)
+        return c, 0.0, None
+
+
+class GeometricMedian(LinearRule):
+    """The geometric median of the clients' rows (:func:`geometric_median_coeffs`).  Config keys
+    ``gm_iters`` (100), ``gm_tol`` (1e-12), ``gm_nu`` (1e-6); ``iterations`` holds the count."""
+
+    def __init__(self, aggregation_config):
+        LinearRule.__init__(self, aggregation_config=aggregation_config)
+        self.gm_iters = aggregation_config.get("gm_iters", 100)
+        self.gm_tol = aggregation_config.get("gm_tol", 1e-12)
+        self.gm_nu = aggregation_config.get("gm_nu", 1e-6)
+        self.iterations = None
+
+    def _coeffs(self, K, w, packets, keep, n):
+        c, self.iterations = geometric_median_coeffs(K, w, self.gm_iters, self.gm_tol, self.gm_nu)
+        return c, 0.0, None
+
+
+class CenteredClip(LinearRule):
+    """Centered clipping around the previous round's aggregate (:func:`centered_clip_coeffs`).
+    Config keys ``cclip_tau`` (required, > 0) and ``cclip_iters`` (3).  ``v`` is the carried
+    device float32 vector: None before the first round (the zero start: no dot call) and after
+    ``reset()``; a round of another length or device raises instead of resetting it."""
+
+    def __init__(self, aggregation_config):
+        LinearRule.__init__(self, aggregation_config=aggregation_config)
+        tau = aggregation_config.get("cclip_tau", None)
+        if tau is None or isinstance(tau, bool) or not isinstance(tau, (int, float, np.floating, np.integer)) \
+                or not tau > 0:
+            raise ValueError(f"cclip_tau must be a number > 0 (got {tau!r})")
+        self.cclip_tau = float(tau)
+        self.cclip_iters = aggregation_config.get("cclip_iters", 3)
+        self.v = None
+
+    def reset(self) -> None:
+        self.v = None
+
+    def _coeffs(self, K, w, packets, keep, n):
+        v = self.v
+        if v is None:
+            a, c = centered_clip_coeffs(K, None, 0.0, self.cclip_tau, self.cclip_iters)
+            return c, 0.0, None
+        if v.numel() != n or v.device != packets[0].val.device:
+            raise ValueError(f"the carried vector has {v.numel()} elements on {v.device}; the round has "
+                             f"{n} on {packets[0].val.device} (reset() starts over)")
+        b, q = self._dot(packets, keep, v)
+        a, c = centered_clip_coeffs(K, b, q, self.cclip_tau, self.cclip_iters)
+        return c, a, v
+
+    def _after(self, agg: torch.Tensor) -> None:
+        self.v = agg.clone()
