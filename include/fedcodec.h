@@ -359,6 +359,67 @@ int fc_packets_dot(const fc_packet_view* views_dev, int m, uint64_t n,
                    double* out /* DEVICE float64[m + 1], 16-B aligned */,
                    void* ws, size_t ws_bytes, fc_stream_t stream);
 
+/* ---- The wire form of FC_FMT_IDXVAL packets: pack, unpack, validate (fc_wire.hip) -----------
+ * A slotted packet reserves 6n + 12 nch + 96 bytes whatever it keeps.  Its wire form is ONE
+ * contiguous byte string that holds the kept entries alone: what a client sends.  Little-endian,
+ * every section 16-B aligned, pad bytes zero (openmsftl_amd/csrc/fc_wire_host.h):
+ *   0     fc_wire_hdr, 128 bytes: uint32 magic ("FCW1"), uint32 version (1), uint64 total_bytes,
+ *         uint64 n_entries (E), uint32 nch, uint32 status, fc_packet_hdr pkt
+ *   128   uint64 qoff[nch]   the slotted word format over the KEPT entries (quarter 1/2/3 starts
+ *                            in bits 0-15 / 16-31 / 32-47, cnt in bits 48-63)
+ *         uint32 start[nch]  exclusive prefix sum of the counts
+ *         uint16 idx[E]      chunk-local, ascending inside each chunk
+ *         float  val[E]      the stored values bit for bit (the decoders apply 1/p from pkt.p)
+ * Kept: exactly the entries fc_packets_gram counts (composite >= T64, the Philox key for native
+ *   rand-k, thresh == 0 keeps every listed entry; the quarter an entry is listed under matches
+ *   its index).  A resolved top-k / native rand-k packet has E == k.
+ * pkt is canonical: the source header's thresh, n, k, index_bits, codec, seed, offset, p, chunk,
+ *   format, key_mode; lower = thresh, n_entries = E (also for mask packets), status = 0,
+ *   n_definite = n_cand = reserved = 0.  The bytes are a function of the kept content and those
+ *   fields alone: a sampled-bracket encode and fc_topk_encode_exact of one gradient pack alike.
+ * fc_wire_bytes(n, E): HOST, the exact size; monotone in E (0 for n == 0 or n, E >= 2^32).
+ *
+ * fc_wire_pack_batch: m packets (views_dev: DEVICE array of m FC_FMT_IDXVAL views with qoff, as
+ *   fc_packets_gram takes them; `weight` ignored) into m wire buffers (jobs_dev: DEVICE array of
+ *   m fc_wire_job: a 16-B aligned DEVICE buffer of at least 128 bytes and its capacity in bytes).
+ *   A source header whose status is not OK: that status goes into the wire `status` and nothing
+ *   else is promised.  A capacity below the packet's size: status FC_STATUS_OVERFLOW, the
+ *   128-byte header alone (total_bytes = the size needed, n_entries = E) and nothing past the
+ *   capacity.  Otherwise exactly total_bytes bytes are written.  Launches: count, scan, compact
+ *   (grid.y = the client; grids from n and m alone; no workgroup waits for another; no atomics):
+ *   two calls give the same bytes.  Stream-ordered, no allocation, no host synchronisation.
+ *   ws: fc_wire_workspace_bytes(n, m) bytes (monotone in n and m), 16-B aligned, needs NO zeroing.
+ * fc_wire_unpack_batch: m wire packets on the device (jobs_dev: buffer and its byte length, as
+ *   the HOST knows it) into m slotted packets (views_dev: the DESTINATION packets, written
+ *   through: idx, val, cnt, qoff, hdr all present, capacity fc_packet_capacity(n)).  Writes the
+ *   listed slot positions, cnt, qoff and hdr (= pkt) only: never the 6n capacity.  Memory safe
+ *   whatever the bytes hold: every read is below the byte length, start and cnt are clamped
+ *   against E and the section ends, every write lands in its chunk's slot; a buffer whose header
+ *   does not fit n or the length becomes an empty packet with status FC_STATUS_OVERFLOW.  The
+ *   index VALUES are not checked here (consumers use them as LDS locations): bytes that come
+ *   from outside pass fc_wire_validate first.
+ * Both: 1 <= m <= 65535, 1 <= n < 2^32, NULL tables: FC_ERR_ARG; a short workspace:
+ *   FC_ERR_WORKSPACE; all before the GPU is touched.
+ * fc_wire_validate: HOST bytes, no GPU.  FC_OK, or FC_ERR_ARG with the reason in
+ *   fc_last_error().  In this order, reading nothing past len: (1) len >= 128, magic, version,
+ *   total_bytes == len; (2) pkt: 1 <= n < 2^32, n == n_expected unless that is 0, k <= n,
+ *   index_bits, chunk, format IDXVAL, codec 1..4, key_mode 0..1, both statuses 0; (3) nch and
+ *   total_bytes == fc_wire_bytes(n, E); (4) per chunk q1 <= q2 <= q3 <= cnt <= 8192, start the
+ *   prefix sum, the counts summing to E == pkt.n_entries; (5) per quarter range strictly
+ *   ascending indices of that quarter with c * 8192 + idx < n; (6) zero pads.  It does not check
+ *   entries against thresh: a listed entry below it is dropped by every decoder. */
+typedef struct fc_wire_job {
+  void* wire;            /* DEVICE wire buffer, 16-B aligned                       */
+  uint64_t bytes;        /* pack: its capacity; unpack: the packet's byte length    */
+} fc_wire_job;           /* 16 bytes */
+uint64_t fc_wire_bytes(uint64_t n, uint64_t n_entries);
+size_t fc_wire_workspace_bytes(uint64_t n, int m);
+int fc_wire_pack_batch(const fc_packet_view* views_dev, const fc_wire_job* jobs_dev, int m,
+                       uint64_t n, void* ws, size_t ws_bytes, fc_stream_t stream);
+int fc_wire_unpack_batch(const fc_wire_job* jobs_dev, const fc_packet_view* views_dev, int m,
+                         uint64_t n, fc_stream_t stream);
+int fc_wire_validate(const void* host_bytes, size_t len, uint64_t n_expected /* 0 = any */);
+
 /* ---- FedAVG over dense rows (gar.py:44 for 'full'): rows = DEVICE array of m row
  * pointers, w = DEVICE fp32[m]. */
 int fc_weighted_sum_dense(const float* const* rows, const float* w, int m, uint64_t n,

@@ -71,6 +71,21 @@ class PermState(ctypes.Structure):
                 ("reserved", ctypes.c_uint32), ("consumed", ctypes.c_uint64)]
 
 
+class WireJob(ctypes.Structure):
+    """fc_wire_job: a device wire buffer and its capacity (pack) or byte length (unpack)."""
+    _fields_ = [("wire", ctypes.c_void_p), ("bytes", ctypes.c_uint64)]
+
+
+class WireHdr(ctypes.Structure):
+    """fc_wire_hdr: the first 128 bytes of a wire packet."""
+    _fields_ = [("magic", ctypes.c_uint32), ("version", ctypes.c_uint32),
+                ("total_bytes", ctypes.c_uint64), ("n_entries", ctypes.c_uint64),
+                ("nch", ctypes.c_uint32), ("status", ctypes.c_uint32), ("pkt", PacketHdr)]
+
+
+WIRE_HDR_BYTES = 128
+assert ctypes.sizeof(WireJob) == 16
+assert ctypes.sizeof(WireHdr) == WIRE_HDR_BYTES
 assert ctypes.sizeof(PermState) == 2520
 assert ctypes.sizeof(PacketHdr) == HDR_BYTES
 assert ctypes.sizeof(EncodeJob) == 64
@@ -113,6 +128,11 @@ SIGNATURES = {
     "fc_packets_gram": (_i32, [_vp, _i32, _u64, _vp, _vp, _sz, _vp]),
     "fc_dot_workspace_bytes": (_sz, [_u64, _i32]),
     "fc_packets_dot": (_i32, [_vp, _i32, _u64, _vp, _vp, _vp, _sz, _vp]),
+    "fc_wire_bytes": (_u64, [_u64, _u64]),
+    "fc_wire_workspace_bytes": (_sz, [_u64, _i32]),
+    "fc_wire_pack_batch": (_i32, [_vp, _vp, _i32, _u64, _vp, _sz, _vp]),
+    "fc_wire_unpack_batch": (_i32, [_vp, _vp, _i32, _u64, _vp]),
+    "fc_wire_validate": (_i32, [_vp, _sz, _u64]),
     "fc_weighted_sum_dense": (_i32, [_vp, _vp, _i32, _u64, _vp, _vp]),
     "fc_weighted_sum_dense_continue": (_i32, [_vp, _vp, _i32, _u64, _vp, _vp]),
     "fc_div_scalar": (_i32, [_vp, _u64, ctypes.c_float, _vp]),

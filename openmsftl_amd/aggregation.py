@@ -49,6 +49,12 @@ GAR (gar.py:44).  Here the rows never become a dense matrix on the common path:
   with those coefficients.  ``"fed_spectral_avg"`` (the reference's class, with its autoencoder
   branch) keeps raising.
 
+* ``Aggregator.aggregate_wire(payloads)`` (:func:`aggregate_wire`) aggregates a round from the
+  clients' wire packets (``Compression.compress_wire``; include/fedcodec.h) instead of their
+  gradients: validated on the host, uploaded, unpacked into slotted packets, then the fold of
+  the "stream" route or the Gram family's ``aggregate_packets``: the same bits, ``agg_path =
+  "wire"``.
+
 ``aggregate_grads`` is a plain function so that :func:`openmsftl_amd.integration.install` can
 bind it onto the REFERENCE ``Aggregator`` class (its ``self.gar`` may then be a reference GAR
 with no ``aggregate_packets``: G is then handed over as the host array the reference builds).
@@ -700,6 +706,133 @@ def aggregate_grads(self, clients: List, input_feature: np.ndarray = None,
     self.agg_grad = agg.cpu().numpy() if isinstance(agg, torch.Tensor) else agg
 
 
+def wire_group(agg, n: int, m: int, dev: torch.device) -> int:
+    """Payloads per fold group of :func:`aggregate_wire`'s FedAvg: the streamed route's own
+    sizing (``pipeline.plan_group`` under :func:`_budget`; a group's wire bytes are smaller than
+    the gradients that budget reserves a ring for)."""
+    from .pipeline import plan_group
+    return plan_group(n, m, _budget(agg, dev))
+
+
+def wire_resident_bytes(n: int, m: int, wire_total: int) -> int:
+    """Device bytes :func:`aggregate_wire` holds at once on the Gram family's path: the round's
+    wire bytes and unpacked packets, the Gram and dot workspaces, the aggregate, a carried vector
+    and the Gram matrix."""
+    from .pipeline import packet_bytes
+    lib = L.load()
+    return (wire_total + m * packet_bytes(n) + int(lib.fc_gram_workspace_bytes(n, m))
+            + int(lib.fc_dot_workspace_bytes(n, m)) + 4 * n + 4 * n + 8 * m * m)
+
+
+def aggregate_wire(self, payloads, n: Optional[int] = None) -> None:
+    """A round from the clients' wire packets (``Compression.compress_wire``; include/fedcodec.h)
+    instead of their gradients: every payload is validated on the host (``fc_wire_validate``, the
+    check of ``codec.wire_from_host``: ``ValueError`` with the reason, before any of the round
+    reaches the GPU), uploaded, unpacked
+    into slotted packets and aggregated.  Sets ``agg_grad`` (host array), ``agg_path = "wire"``
+    and ``curr_G = None``.
+
+    * ``fed_avg``: any number of payloads, folded in row order in groups sized by the device
+      budget; bit-equal to the "stream" route of ``aggregate_grads`` on the same clients.
+    * ``krum``, ``spectral_gram`` / ``geometric_median`` / ``centered_clip`` and
+      ``pc_analysis: "gram"``: at most ``FC_GRAM_MAX_M`` payloads, all resident within the budget;
+      ``codec.gram`` then ``gar.aggregate_packets`` exactly as the "gram" route does.
+    Hierarchies, payloads of differing n and a round that does not fit raise
+    ``NotImplementedError`` naming the condition."""
+    def no(why: str):
+        raise NotImplementedError(f"aggregate_wire needs {why}")
+    payloads = list(payloads)
+    m = len(payloads)
+    if m == 0:
+        raise Exception('Client List is Empty')
+    if self.analyze_pc is True:
+        no("pc_analysis off or 'gram' (the randomized SVD of G is outside the hot path)")
+    if self.num_hierarchies != 0:
+        no("no hierarchies (num_hierarchies == 0)")
+    gar = self.gar
+    family = gram_wanted(self)
+    if not family and type(gar) is not FedAvg:
+        no("the device FedAvg, Krum, spectral_gram, geometric_median or centered_clip")
+    cfg = getattr(self, "aggregation_config", None) or {}
+    if cfg.get("devices", DEFAULT_DEVICES) not in (None, 1):
+        no("one device")
+    w = getattr(gar, "gradient_weights", None)
+    if w is not None and np.asarray(w).dtype != np.float32:
+        no("float32 GAR weights")
+    if family and m > L.FC_GRAM_MAX_M:
+        no(f"at most {L.FC_GRAM_MAX_M} payloads for the gram route (got {m})")
+    # ---- the host's part: every payload validated, one common n ----
+    hosts, total = [], 0
+    for i, raw in enumerate(payloads):
+        try:
+            a, h = codec._wire_check(raw)
+        except ValueError as e:
+            raise ValueError(f"payload {i}: {e}") from None
+        hn = int(h.pkt.n)
+        if n is None:
+            n = hn
+        if hn != int(n):
+            no(f"payloads of one length n (payload {i} has n = {hn}, not {int(n)})")
+        hosts.append((a, h))
+        total += (a.size + 255) & ~255
+    n = int(n)
+    b = cfg.get("device_budget_bytes")
+    if family and b and wire_resident_bytes(n, m, total) > int(b):
+        no(f"the round's packets to fit device_budget_bytes ({wire_resident_bytes(n, m, total)}"
+           f" > {int(b)} bytes)")
+    # ---- the device's part ----
+    dev = _device_of(self)
+    self.agg_path = "wire"
+    self.curr_G = None
+    cache = self.__dict__.setdefault("_wire_packets", {})
+
+    def packets_for(count: int):
+        pk = cache.get((n, dev))
+        if pk is None or len(pk) < count:
+            for key in [k for k in cache if k != "slab"]:   # one shape at a time
+                del cache[key]
+            pk = cache[(n, dev)] = codec.Packet.alloc_batch(n, count, L.FC_FMT_IDXVAL, dev)
+        return pk[:count]
+
+    def upload(part):
+        """The payloads of one group into one cached device slab (256-byte aligned each)."""
+        offs = np.concatenate([[0], np.cumsum([(a.size + 255) & ~255 for a, _ in part])])
+        slab = cache.get("slab")
+        if slab is None or slab.device != dev or slab.numel() < int(offs[-1]):
+            cache.pop("slab", None)
+            slab = cache["slab"] = torch.empty(int(offs[-1]), dtype=torch.uint8, device=dev)
+        return [codec._wire_upload(a, h, dev, out=slab[int(o): int(o) + a.size])
+                for (a, h), o in zip(part, offs)]
+
+    if family:
+        need = wire_resident_bytes(n, m, total)
+        if need > _budget(self, dev):
+            no(f"the round's packets to fit device_budget_bytes ({need} > {_budget(self, dev)} bytes)")
+        wires = upload(hosts)
+        pk = codec.unpack(wires, packets_for(m))
+        del wires
+        gram = codec.gram(pk)
+        if isinstance(gar, (Krum, LinearRule)):
+            out = gar.aggregate_packets(pk, gram=gram)
+        else:
+            wts = gar._weights(m, np.float32)                       # gar.py:37-42 (persisted)
+            out = codec.decode_accumulate(pk, [float(x) for x in wts])
+        if getattr(self, "analyze_pc", False) == "gram":
+            gar.Sigma_tracked.append(gram_singular_values(gram.cpu().numpy()))
+    else:
+        wts = gar._weights(m, np.float32)                           # gar.py:37-42 (persisted)
+        group = wire_group(self, n, m, dev)
+        out = torch.empty(n, dtype=torch.float32, device=dev)
+        for gi, s in enumerate(range(0, m, group)):
+            part = hosts[s:s + group]
+            wires = upload(part)
+            pk = codec.unpack(wires, packets_for(len(part)))
+            codec.decode_accumulate(pk, [float(x) for x in wts[s:s + len(part)]], out=out,
+                                    continue_sum=gi > 0)
+            del wires
+    self.agg_grad = out.cpu().numpy()
+
+
 class Aggregator:
     """aggregation.py:19-93 — the aggregation hot path of the reference's ``Aggregator``.
 
@@ -716,7 +849,7 @@ class Aggregator:
         self.gar = self.__get_gar()
         self.curr_G = None
         self.agg_grad = None
-        self.agg_path = None                # "stream" | "dense-fold" | "dense" | "ef-batch" | "gram": the last call's path
+        self.agg_path = None                # "stream" | "dense-fold" | "dense" | "ef-batch" | "gram" | "wire": the last call's path
         self.agg_draws = None               # streamed np.random draws: "device-mt" | "device-perm" | "host" | None
         self.analyze_pc = self.aggregation_config.get("pc_analysis", False)
         self.num_hierarchies = self.aggregation_config.get("num_hierarchies", 0)
@@ -742,9 +875,10 @@ class Aggregator:
         raise NotImplementedError
 
     aggregate_grads = aggregate_grads
+    aggregate_wire = aggregate_wire
 
     def update_model(self):
         raise NotImplementedError("model update is outside the codec hot path (DESIGN.md §8)")
 
 
-__all__ = ["Aggregator", "Compression", "aggregate_grads"]
+__all__ = ["Aggregator", "Compression", "aggregate_grads", "aggregate_wire"]

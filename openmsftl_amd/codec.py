@@ -8,6 +8,8 @@
     agg = decode_accumulate(pkts, w)       # aggregation.py:61-63 + gar.py:44, bit-exact fp32
     gm  = gram(pkts)                       # G @ G.T in float64 straight from the packets
     b   = dot_dense(pkts, v)               # [G @ v, v @ v] in float64 (v=None: row sums, n)
+    w   = pack(pkt); raw = w.tobytes()     # the compact wire form: the kept entries alone
+    pkt = unpack(wire_from_host(raw))      # validated host bytes back into a slotted packet
 
 Packets live on the GPU in the slotted layout of include/fedcodec.h: chunk c (8192 elements)
 lists its entries, ascending, at ``[c*8192, c*8192 + cnt[c])`` of ``idx``/``val`` (or
@@ -19,6 +21,7 @@ from __future__ import annotations
 import bisect
 import ctypes
 import threading
+import warnings
 import weakref
 from dataclasses import dataclass
 from typing import Optional, Sequence
@@ -855,11 +858,7 @@ def gram(packets: Sequence[Packet], out: Optional[torch.Tensor] = None) -> torch
     m, n, dev = len(packets), packets[0].n, packets[0].val.device
     if m > L.FC_GRAM_MAX_M:
         raise ValueError(f"gram takes at most {L.FC_GRAM_MAX_M} packets (got {m})")
-    for p in packets:
-        if p.n != n:
-            raise ValueError("packets must share n")
-        if p.fmt != L.FC_FMT_IDXVAL or p.idx is None or p.qoff is None:
-            raise ValueError("gram needs idx/val packets (FC_FMT_IDXVAL) with quarter offsets")
+    _check_idxval_packets(packets)
     lib = L.load()
     if out is None:
         out = torch.empty((m, m), dtype=torch.float64, device=dev)
@@ -908,11 +907,7 @@ def dot_dense(packets: Sequence[Packet], v: Optional[torch.Tensor] = None,
     m, n, dev = len(packets), packets[0].n, packets[0].val.device
     if m > L.FC_GRAM_MAX_M:
         raise ValueError(f"gram takes at most {L.FC_GRAM_MAX_M} packets (got {m})")
-    for p in packets:
-        if p.n != n:
-            raise ValueError("packets must share n")
-        if p.fmt != L.FC_FMT_IDXVAL or p.idx is None or p.qoff is None:
-            raise ValueError("gram needs idx/val packets (FC_FMT_IDXVAL) with quarter offsets")
+    _check_idxval_packets(packets)
     if v is not None:
         if (not isinstance(v, torch.Tensor) or v.dtype != torch.float32 or v.device != dev
                 or v.numel() != n or not v.is_contiguous() or v.data_ptr() % 16):
@@ -930,6 +925,233 @@ def dot_dense(packets: Sequence[Packet], v: Optional[torch.Tensor] = None,
     L.check(lib.fc_packets_dot(_vp(views), m, n, _vp(v), _vp(out), _vp(ws.buf), ws.nbytes,
                                _stream(dev)), "fc_packets_dot")
     return out
+
+
+# ---- the wire form of idx/val packets (csrc/fc_wire.hip, include/fedcodec.h) ------------------
+@dataclass
+class WirePacket:
+    """One packet as the contiguous byte string a client sends (include/fedcodec.h): the kept
+    entries alone.  ``buf`` is a 16-byte aligned uint8 device tensor whose first ``nbytes`` bytes
+    are the packet; ``k`` is the header's k (what :func:`unpack` gives ``Packet.k``)."""
+    n: int
+    buf: torch.Tensor
+    nbytes: int
+    k: int = 0
+
+    def tobytes(self) -> bytes:
+        """The packet's bytes on the host (synchronises)."""
+        return self.buf[: self.nbytes].cpu().numpy().tobytes()
+
+
+class WireWorkspace:
+    """Per-(device, stream) scratch of :func:`pack` (counts and prefix sums; needs no zeroing)."""
+
+    _cache: dict = {}
+
+    def __init__(self, nbytes: int, device: torch.device):
+        self.nbytes = nbytes
+        self.buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+    @classmethod
+    def get(cls, n: int, m: int, device: torch.device) -> "WireWorkspace":
+        need = int(L.load().fc_wire_workspace_bytes(n, m))
+        key = (device.index if device.index is not None else torch.cuda.current_device(),
+               torch.cuda.current_stream(device).cuda_stream)
+        ws = cls._cache.get(key)
+        if ws is None or ws.nbytes < need:
+            ws = cls(need, device)
+            cls._cache[key] = ws
+        return ws
+
+
+def wire_bytes(n: int, entries: int) -> int:
+    """The exact size of a wire packet of length n with ``entries`` kept entries (host)."""
+    return int(L.load().fc_wire_bytes(int(n), int(entries)))
+
+
+def _wire_jobs(buffers: Sequence[torch.Tensor], sizes: Sequence[int], device) -> torch.Tensor:
+    arr = (L.WireJob * len(buffers))(*[L.WireJob(wire=b.data_ptr(), bytes=int(s))
+                                       for b, s in zip(buffers, sizes)])
+    host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
+    return host.to(device)
+
+
+def _check_idxval_packets(packets: Sequence[Packet]):
+    """What :func:`gram`, :func:`dot_dense` and :func:`pack` ask of their packets: (n, device)."""
+    if not packets:
+        raise ValueError("no packets")
+    n, dev = packets[0].n, packets[0].val.device
+    for p in packets:
+        if p.n != n:
+            raise ValueError("packets must share n")
+        if p.fmt != L.FC_FMT_IDXVAL or p.idx is None or p.qoff is None:
+            raise ValueError("gram needs idx/val packets (FC_FMT_IDXVAL) with quarter offsets")
+    return n, dev
+
+
+def _check_wire_buffer(b, device, what: str):
+    if (not isinstance(b, torch.Tensor) or b.dtype != torch.uint8 or b.device != device
+            or b.dim() != 1 or not b.is_contiguous() or b.data_ptr() % 16
+            or b.numel() < L.WIRE_HDR_BYTES):
+        raise ValueError(f"{what} must be a contiguous 16-byte aligned uint8 tensor of at least "
+                         f"{L.WIRE_HDR_BYTES} bytes on the packets' device")
+
+
+def pack_into(packets: Sequence[Packet], buffers: Sequence[torch.Tensor],
+              capacities: Optional[Sequence[int]] = None) -> list:
+    """fc_wire_pack_batch: packet i into ``buffers[i]`` (uint8 device tensors, 16-byte aligned),
+    of which at most ``capacities[i]`` bytes (default: all) may be written.  One launch chain for
+    the batch, then ONE synchronising read of the m wire headers.  Returns the m ``L.WireHdr``;
+    nothing is raised for a status that is not OK (:func:`pack` does that)."""
+    n, dev = _check_idxval_packets(packets)
+    m = len(packets)
+    if len(buffers) != m or (capacities is not None and len(capacities) != m):
+        raise ValueError("one buffer (and one capacity) per packet")
+    for b in buffers:
+        _check_wire_buffer(b, dev, "a wire buffer")
+    caps = [b.numel() for b in buffers] if capacities is None else [int(c) for c in capacities]
+    if any(not L.WIRE_HDR_BYTES <= c <= b.numel() for c, b in zip(caps, buffers)):
+        raise ValueError(f"a capacity must lie between {L.WIRE_HDR_BYTES} and its buffer's size")
+    lib = L.load()
+    ws = WireWorkspace.get(n, m, dev)
+    views = views_tensor(packets, [1.0] * m, dev)
+    jobs = _wire_jobs(buffers, caps, dev)
+    L.check(lib.fc_wire_pack_batch(_vp(views), _vp(jobs), m, n, _vp(ws.buf), ws.nbytes,
+                                   _stream(dev)), "fc_wire_pack_batch")
+    raw = torch.stack([b[: L.WIRE_HDR_BYTES] for b in buffers]).cpu().numpy()
+    return [L.WireHdr.from_buffer_copy(raw[i].tobytes()) for i in range(m)]
+
+
+def pack(packets, entries=None):
+    """The wire form of one idx/val packet or of a sequence of them (one launch chain):
+    a :class:`WirePacket`, or a list of them.  Only the entries the decoders keep are packed.
+
+    Each buffer is sized for ``entries`` kept entries (an int, or one per packet) when given;
+    otherwise for ``Packet.k`` if the packet came from a top-k / native rand-k encode (resolved:
+    it keeps exactly k), and otherwise for its listed entries, found by one synchronising read of
+    the counts.  Raises ``FedCodecError`` if a wire status is not OK (a source packet that is not
+    resolved, ``entries`` too small)."""
+    single = isinstance(packets, Packet)
+    pk = [packets] if single else list(packets)
+    n, dev = _check_idxval_packets(pk)
+    m = len(pk)
+    if entries is not None:
+        ent = [int(entries)] * m if isinstance(entries, (int, np.integer)) else [int(e) for e in entries]
+        if len(ent) != m or any(e < 0 for e in ent):
+            raise ValueError("entries: one non-negative count, or one per packet")
+    else:
+        ent = [int(p.k) if hasattr(p, "_enc") else None for p in pk]
+        unknown = [i for i, e in enumerate(ent) if e is None]
+        if unknown:                                    # listed >= kept: one read for all of them
+            tot = torch.stack([pk[i].cnt.sum(dtype=torch.int64) for i in unknown]).cpu().tolist()
+            for i, t in zip(unknown, tot):
+                ent[i] = int(t)
+    lib = L.load()
+    caps = [int(lib.fc_wire_bytes(n, min(e, n))) for e in ent]
+    offs = np.concatenate([[0], np.cumsum([(c + 255) & ~255 for c in caps])]).astype(np.int64)
+    slab = torch.empty(int(offs[-1]), dtype=torch.uint8, device=dev)
+    bufs = [slab[int(offs[i]): int(offs[i]) + caps[i]] for i in range(m)]
+    hdrs = pack_into(pk, bufs)
+    out = []
+    for i, (h, b) in enumerate(zip(hdrs, bufs)):
+        if h.status != L.FC_STATUS_OK:
+            raise L.FedCodecError(f"wire packet {i}: status {h.status}"
+                                  + (f" ({h.n_entries} entries kept, room for {ent[i]})"
+                                     if h.status == L.FC_STATUS_OVERFLOW else ""))
+        out.append(WirePacket(n=n, buf=b, nbytes=int(h.total_bytes), k=int(h.pkt.k)))
+    return out[0] if single else out
+
+
+def wire_from_host(data, n: Optional[int] = None, device=None) -> WirePacket:
+    """Host bytes (``bytes``, a NumPy uint8 array or a CPU uint8 tensor) as a :class:`WirePacket`
+    on ``device``: ALWAYS through ``fc_wire_validate`` first (``ValueError`` with the library's
+    reason; no device work has started then), then the H2D copy.  ``n``: the length the packet
+    must have.  The only way host bytes become a WirePacket."""
+    return _wire_upload(*_wire_check(data, n), device)
+
+
+def _wire_check(data, n: Optional[int] = None):
+    """fc_wire_validate on host bytes: (the bytes as a uint8 array, their ``L.WireHdr``), or
+    ``ValueError`` with the library's reason.  Touches no device."""
+    if isinstance(data, torch.Tensor):
+        if data.is_cuda or data.dtype != torch.uint8 or data.dim() != 1:
+            raise TypeError("data must be bytes, a 1-D NumPy uint8 array or a 1-D CPU uint8 tensor")
+        arr = data.contiguous().numpy()
+    elif isinstance(data, (bytes, bytearray, memoryview)):
+        arr = np.frombuffer(data, dtype=np.uint8)
+    elif isinstance(data, np.ndarray) and data.dtype == np.uint8 and data.ndim == 1:
+        arr = np.ascontiguousarray(data)
+    else:
+        raise TypeError("data must be bytes, a 1-D NumPy uint8 array or a 1-D CPU uint8 tensor")
+    if n is not None and int(n) < 1:
+        raise ValueError("n must be at least 1")
+    lib = L.load()
+    rc = lib.fc_wire_validate(ctypes.c_void_p(arr.ctypes.data), arr.size, int(n) if n else 0)
+    if rc != L.FC_OK:
+        msg = lib.fc_last_error()
+        raise ValueError(msg.decode() if msg else "wire: invalid packet")
+    return arr, L.WireHdr.from_buffer_copy(arr[: L.WIRE_HDR_BYTES].tobytes())
+
+
+def _wire_upload(arr: np.ndarray, hdr, device=None, out: Optional[torch.Tensor] = None) -> WirePacket:
+    """The H2D copy of bytes :func:`_wire_check` has passed (into ``out``, a 16-byte aligned
+    uint8 device tensor of their size, when given)."""
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    if arr.flags.writeable:
+        host = torch.from_numpy(arr)
+    else:                                          # e.g. bytes: only ever read, so no host copy
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", UserWarning)
+            host = torch.frombuffer(arr, dtype=torch.uint8)
+    if out is None:
+        buf = host.to(dev)
+    else:
+        _check_wire_buffer(out, dev, "out")
+        if out.numel() != arr.size:
+            raise ValueError("out must have the payload's size")
+        buf = out.copy_(host)
+    return WirePacket(n=int(hdr.pkt.n), buf=buf, nbytes=arr.size, k=int(hdr.pkt.k))
+
+
+def unpack(wires, packets=None):
+    """Wire packets back into ordinary slotted :class:`Packet` objects (fc_wire_unpack_batch, one
+    launch for the batch, no synchronisation): freshly allocated, or ``packets`` reused.  Only
+    the listed slot positions, the counts, the quarter offsets and the header are written."""
+    single = isinstance(wires, WirePacket)
+    ws = [wires] if single else list(wires)
+    if not ws:
+        raise ValueError("no packets")
+    n, dev = ws[0].n, ws[0].buf.device
+    for w in ws:
+        if w.n != n:
+            raise ValueError("packets must share n")
+        _check_wire_buffer(w.buf, dev, "a wire packet's buffer")
+        if not L.WIRE_HDR_BYTES <= w.nbytes <= w.buf.numel():
+            raise ValueError("a wire packet's nbytes lies outside its buffer")
+    m = len(ws)
+    lib = L.load()
+    if packets is None:
+        pk = Packet.alloc_batch(n, m, L.FC_FMT_IDXVAL, dev)
+    else:
+        pk = [packets] if isinstance(packets, Packet) else list(packets)
+        if len(pk) != m:
+            raise ValueError("one destination packet per wire packet")
+        cap = int(lib.fc_packet_capacity(n))
+        for p in pk:
+            if (p.n != n or p.fmt != L.FC_FMT_IDXVAL or p.idx is None or p.qoff is None
+                    or p.capacity < cap or p.val.device != dev):
+                raise ValueError("a destination must be an idx/val packet of length n with "
+                                 "quarter offsets on the wire packets' device")
+    for p, w in zip(pk, ws):
+        p.k = w.k
+        p.__dict__.pop("_enc", None)               # no encode behind it: pack() reads its counts
+        p._dense_only = False
+        p.retried = False
+    views = views_tensor(pk, [1.0] * m, dev)
+    jobs = _wire_jobs([w.buf for w in ws], [w.nbytes for w in ws], dev)
+    L.check(lib.fc_wire_unpack_batch(_vp(jobs), _vp(views), m, n, _stream(dev)),
+            "fc_wire_unpack_batch")
+    return pk[0] if single else pk
 
 
 def weighted_sum_dense(rows, weights: torch.Tensor, out: Optional[torch.Tensor] = None,

@@ -212,6 +212,16 @@ class Compression:
         :meth:`get_residual` before the first call and :meth:`set_residual` it back before the
         second.  float32 gradients only; the length may not change between calls
         (:meth:`reset_residual` starts over)."""
+        on_device = isinstance(grad, torch.Tensor)
+        pkt = self._top_ef_packet(grad)
+        if pkt is None:                            # an empty gradient
+            return grad.clone() if on_device else np.zeros_like(grad)
+        out = codec.decode(pkt)
+        return out if on_device else out.cpu().numpy()
+
+    def _top_ef_packet(self, grad):
+        """The packet behind :meth:`_top_ef` (None for an empty gradient): the residual advances
+        here, once per call, whether the caller wants the dense q or the packet's wire form."""
         L.load()
         on_device = isinstance(grad, torch.Tensor)
         g = self._to_device(grad)
@@ -220,7 +230,7 @@ class Compression:
                                       f"(got {g.dtype})")
         n = g.numel()
         if n == 0:
-            return grad.clone() if on_device else np.zeros_like(grad)
+            return None
         if g.data_ptr() % 16:
             g = g.clone()
         res = self._residual
@@ -236,8 +246,34 @@ class Compression:
         pkt, new = codec.encode_top_ef(g, res, k, residual_out=spare)
         self._residual, self._residual_spare = new, res
         self._residual_numpy = not on_device
-        out = codec.decode(pkt)
-        return out if on_device else out.cpu().numpy()
+        return pkt
+
+    def compress_wire(self, grad) -> bytes:
+        """What a client sends instead of the dense ``compress(grad)``: the 'top' packet of a 1-D
+        float32 gradient (NumPy array or CUDA tensor) in its wire form (include/fedcodec.h:
+        encode, resolve, ``codec.pack``), as ``bytes``.  With ``"error_feedback": True`` the
+        packet is :meth:`_top_ef`'s and the residual advances exactly as ``compress`` advances
+        it.  ``Aggregator.aggregate_wire`` takes a round of these.  Other codecs raise
+        ``NotImplementedError`` (``codec.pack`` itself takes any idx/val packet)."""
+        fn = self.compression_function
+        if fn != 'top':
+            raise NotImplementedError(f"compress_wire is built for 'top' only (got {fn!r})")
+        L.load()
+        if self.error_feedback:
+            pkt = self._top_ef_packet(grad)
+            if pkt is None:
+                raise ValueError("compress_wire: empty gradient")
+        else:
+            g = self._to_device(grad)
+            if g.dtype != torch.float32:
+                raise NotImplementedError(f"compress_wire handles float32 gradients only (got {g.dtype})")
+            n = g.numel()
+            if n == 0:
+                raise ValueError("compress_wire: empty gradient")
+            if g.data_ptr() % 16:
+                g = g.clone()
+            pkt = codec.encode_top(g, kept_count(self.fraction_coordinates, n))
+        return codec.pack(pkt).tobytes()
 
     # the two hooks of a batch driver (aggregation's "ef-batch" route): the state advances
     # exactly once per round, in _ef_commit, and not at all when the round fails before it

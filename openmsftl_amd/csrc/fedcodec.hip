@@ -11,3 +11,4 @@
 #include "fc_ef.hip"
 #include "fc_mt.hip"
 #include "fc_perm.hip"
+#include "fc_wire.hip"
