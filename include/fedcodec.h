@@ -407,7 +407,26 @@ int fc_packets_dot(const fc_packet_view* views_dev, int m, uint64_t n,
  *   total_bytes == fc_wire_bytes(n, E); (4) per chunk q1 <= q2 <= q3 <= cnt <= 8192, start the
  *   prefix sum, the counts summing to E == pkt.n_entries; (5) per quarter range strictly
  *   ascending indices of that quarter with c * 8192 + idx < n; (6) zero pads.  It does not check
- *   entries against thresh: a listed entry below it is dropped by every decoder. */
+ *   entries against thresh: a listed entry below it is dropped by every decoder.
+ * fc_wire_fold (fc_wire_fold.hip): the FedAVG of m wire packets on the device without unpacking
+ *   them.  jobs_dev: DEVICE array of m {wire buffer, byte length as the HOST knows it}, as
+ *   fc_wire_unpack_batch takes it; weights_dev: DEVICE fp32[m]; acc: n floats, 16-B aligned,
+ *   started from +0 or, with continue_sum != 0, continued.  For every buffer, whatever its bytes
+ *   hold, acc gets the bits that fc_wire_unpack_batch into fresh packets followed by
+ *   fc_decode_accumulate (fc_decode_accumulate_continue) with the same weights would give: the
+ *   decoders' keep rule per entry (a listed entry below thresh is dropped), 1/p for
+ *   dropout-unbiased, NaN for the coordinates a p == 0 packet does not keep, a buffer whose header
+ *   does not fit n or the length a packet with no entries.  Memory safe whatever the bytes hold:
+ *   the header is read only when the length is >= 128; both tables and the entries are read only
+ *   when fc_wire_bytes(n, E) <= the length; start and the quarter offsets are clamped against E
+ *   and each other as the unpack clamps them, so every read is below the byte length; every LDS
+ *   location is masked into or compared against its 2048-element quarter.  As for the unpack,
+ *   the index VALUES are not checked: bytes from outside pass fc_wire_validate first.
+ *   1 <= m <= 65535: launches of at most 128 packets, each continuing the same left-to-right
+ *   sum, so the result does not depend on how a round is cut into calls.  One workgroup per
+ *   chunk, no workgroup waits for another, no atomics on acc: two calls give the same bits.
+ *   Stream-ordered, no allocation, no workspace, no host synchronisation.  NULL tables or acc,
+ *   m or n out of range, a misaligned acc: FC_ERR_ARG before the GPU is touched. */
 typedef struct fc_wire_job {
   void* wire;            /* DEVICE wire buffer, 16-B aligned                       */
   uint64_t bytes;        /* pack: its capacity; unpack: the packet's byte length    */
@@ -419,6 +438,8 @@ int fc_wire_pack_batch(const fc_packet_view* views_dev, const fc_wire_job* jobs_
 int fc_wire_unpack_batch(const fc_wire_job* jobs_dev, const fc_packet_view* views_dev, int m,
                          uint64_t n, fc_stream_t stream);
 int fc_wire_validate(const void* host_bytes, size_t len, uint64_t n_expected /* 0 = any */);
+int fc_wire_fold(const fc_wire_job* jobs_dev, const float* weights_dev, int m, uint64_t n,
+                 float* acc, int continue_sum, fc_stream_t stream);
 
 /* ---- FedAVG over dense rows (gar.py:44 for 'full'): rows = DEVICE array of m row
  * pointers, w = DEVICE fp32[m]. */

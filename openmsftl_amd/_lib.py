@@ -133,6 +133,7 @@ SIGNATURES = {
     "fc_wire_pack_batch": (_i32, [_vp, _vp, _i32, _u64, _vp, _sz, _vp]),
     "fc_wire_unpack_batch": (_i32, [_vp, _vp, _i32, _u64, _vp]),
     "fc_wire_validate": (_i32, [_vp, _sz, _u64]),
+    "fc_wire_fold": (_i32, [_vp, _vp, _i32, _u64, _vp, _i32, _vp]),
     "fc_weighted_sum_dense": (_i32, [_vp, _vp, _i32, _u64, _vp, _vp]),
     "fc_weighted_sum_dense_continue": (_i32, [_vp, _vp, _i32, _u64, _vp, _vp]),
     "fc_div_scalar": (_i32, [_vp, _u64, ctypes.c_float, _vp]),

@@ -53,7 +53,9 @@ GAR (gar.py:44).  Here the rows never become a dense matrix on the common path:
   clients' wire packets (``Compression.compress_wire``; include/fedcodec.h) instead of their
   gradients: validated on the host, uploaded, unpacked into slotted packets, then the fold of
   the "stream" route or the Gram family's ``aggregate_packets``: the same bits, ``agg_path =
-  "wire"``.
+  "wire"``.  ``aggregation_config["wire_fold"] = True`` (default off) folds FedAvg straight from
+  the uploaded wire bytes instead (``codec.fold_wire``, no slotted packets): the same bits,
+  ``agg_path = "wire-fold"``.
 
 ``aggregate_grads`` is a plain function so that :func:`openmsftl_amd.integration.install` can
 bind it onto the REFERENCE ``Aggregator`` class (its ``self.gar`` may then be a reference GAR
@@ -724,6 +726,33 @@ def wire_resident_bytes(n: int, m: int, wire_total: int) -> int:
             + int(lib.fc_dot_workspace_bytes(n, m)) + 4 * n + 4 * n + 8 * m * m)
 
 
+def _wire_no(why: str):
+    raise NotImplementedError(f"aggregate_wire needs {why}")
+
+
+def wire_fold_groups(sizes, n: int, budget_bytes: int) -> List[range]:
+    """The payloads of a ``"wire_fold"`` round cut into consecutive groups, greedily: a group's
+    sizes, each rounded up to 256 bytes (its place in the device slab), plus ``4 n`` for the
+    aggregate stay within ``budget_bytes``; a group holds at most 65535 payloads (one
+    ``fc_wire_fold`` call) and never fewer than one.  A single payload that does not fit raises
+    ``NotImplementedError`` naming both numbers.  The aggregate cannot depend on the cut: the sum
+    is strictly left to right, and a sum started from +0 never holds -0.0."""
+    room = int(budget_bytes) - 4 * int(n)
+    groups, first, used = [], 0, 0
+    for i, b in enumerate(sizes):
+        r = (int(b) + 255) & ~255
+        if r > room:
+            _wire_no(f"payload {i} and the aggregate to fit device_budget_bytes "
+                     f"({r + 4 * int(n)} > {int(budget_bytes)} bytes)")
+        if i > first and (used + r > room or i - first == 65535):
+            groups.append(range(first, i))
+            first, used = i, 0
+        used += r
+    if len(sizes) > first:
+        groups.append(range(first, len(sizes)))
+    return groups
+
+
 def aggregate_wire(self, payloads, n: Optional[int] = None) -> None:
     """A round from the clients' wire packets (``Compression.compress_wire``; include/fedcodec.h)
     instead of their gradients: every payload is validated on the host (``fc_wire_validate``, the
@@ -734,13 +763,17 @@ def aggregate_wire(self, payloads, n: Optional[int] = None) -> None:
 
     * ``fed_avg``: any number of payloads, folded in row order in groups sized by the device
       budget; bit-equal to the "stream" route of ``aggregate_grads`` on the same clients.
+      With ``aggregation_config["wire_fold"] = True`` (default ``False``) a group's payloads are
+      uploaded and folded as they are (``codec.fold_wire``): no slotted packets are reserved or
+      written, the groups are :func:`wire_fold_groups` of the payload sizes, the bits are the
+      same and ``agg_path = "wire-fold"``.  The key leaves the Gram family below untouched:
+      those consumers read slotted packets, so they still unpack and answer ``"wire"``.
     * ``krum``, ``spectral_gram`` / ``geometric_median`` / ``centered_clip`` and
       ``pc_analysis: "gram"``: at most ``FC_GRAM_MAX_M`` payloads, all resident within the budget;
       ``codec.gram`` then ``gar.aggregate_packets`` exactly as the "gram" route does.
     Hierarchies, payloads of differing n and a round that does not fit raise
     ``NotImplementedError`` naming the condition."""
-    def no(why: str):
-        raise NotImplementedError(f"aggregate_wire needs {why}")
+    no = _wire_no
     payloads = list(payloads)
     m = len(payloads)
     if m == 0:
@@ -819,6 +852,15 @@ def aggregate_wire(self, payloads, n: Optional[int] = None) -> None:
             out = codec.decode_accumulate(pk, [float(x) for x in wts])
         if getattr(self, "analyze_pc", False) == "gram":
             gar.Sigma_tracked.append(gram_singular_values(gram.cpu().numpy()))
+    elif cfg.get("wire_fold", False):
+        wts = gar._weights(m, np.float32)                           # gar.py:37-42 (persisted)
+        groups = wire_fold_groups([a.size for a, _ in hosts], n, _budget(self, dev))
+        self.agg_path = "wire-fold"
+        out = torch.empty(n, dtype=torch.float32, device=dev)
+        for gi, g in enumerate(groups):
+            wires = upload(hosts[g.start:g.stop])
+            codec.fold_wire(wires, wts[g.start:g.stop], out=out, continue_sum=gi > 0)
+            del wires
     else:
         wts = gar._weights(m, np.float32)                           # gar.py:37-42 (persisted)
         group = wire_group(self, n, m, dev)
@@ -849,7 +891,7 @@ class Aggregator:
         self.gar = self.__get_gar()
         self.curr_G = None
         self.agg_grad = None
-        self.agg_path = None                # "stream" | "dense-fold" | "dense" | "ef-batch" | "gram" | "wire": the last call's path
+        self.agg_path = None                # "stream" | "dense-fold" | "dense" | "ef-batch" | "gram" | "wire" | "wire-fold": the last call's path
         self.agg_draws = None               # streamed np.random draws: "device-mt" | "device-perm" | "host" | None
         self.analyze_pc = self.aggregation_config.get("pc_analysis", False)
         self.num_hierarchies = self.aggregation_config.get("num_hierarchies", 0)

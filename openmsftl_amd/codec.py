@@ -10,6 +10,7 @@
     b   = dot_dense(pkts, v)               # [G @ v, v @ v] in float64 (v=None: row sums, n)
     w   = pack(pkt); raw = w.tobytes()     # the compact wire form: the kept entries alone
     pkt = unpack(wire_from_host(raw))      # validated host bytes back into a slotted packet
+    agg = fold_wire(wires, w)              # decode_accumulate(unpack(wires), w) without the unpack
 
 Packets live on the GPU in the slotted layout of include/fedcodec.h: chunk c (8192 elements)
 lists its entries, ascending, at ``[c*8192, c*8192 + cnt[c])`` of ``idx``/``val`` (or
@@ -1152,6 +1153,41 @@ def unpack(wires, packets=None):
     L.check(lib.fc_wire_unpack_batch(_vp(jobs), _vp(views), m, n, _stream(dev)),
             "fc_wire_unpack_batch")
     return pk[0] if single else pk
+
+
+def fold_wire(wires: Sequence[WirePacket], weights, out: Optional[torch.Tensor] = None,
+              continue_sum: bool = False) -> torch.Tensor:
+    """FedAVG straight from wire packets (fc_wire_fold): the bits of
+    ``decode_accumulate(unpack(wires), weights, ...)`` without the slotted packets in between.
+    Each packet's bytes are read once; no synchronisation.
+
+    ``continue_sum=True`` folds the packets into the partial sum already in ``out``."""
+    ws = list(wires)
+    if not ws:
+        raise ValueError("no packets")
+    n, dev = ws[0].n, ws[0].buf.device
+    if any(w.n != n for w in ws):
+        raise ValueError("packets must share n")
+    weights = [float(x) for x in weights]
+    if len(weights) != len(ws):
+        raise ValueError("one weight per packet")
+    if out is None and continue_sum:
+        raise ValueError("continue_sum needs the partial sum in `out`")
+    for w in ws:
+        _check_wire_buffer(w.buf, dev, "a wire packet's buffer")
+        if not L.WIRE_HDR_BYTES <= w.nbytes <= w.buf.numel():
+            raise ValueError("a wire packet's nbytes lies outside its buffer")
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=dev)
+    _require_cuda_f32(out, "out")
+    if out.numel() != n:
+        raise ValueError("out must have n elements")
+    lib = L.load()
+    jobs = _wire_jobs([w.buf for w in ws], [w.nbytes for w in ws], dev)
+    wts = torch.from_numpy(np.asarray(weights, dtype=np.float32)).to(dev)
+    L.check(lib.fc_wire_fold(_vp(jobs), _vp(wts), len(ws), n, _vp(out), int(bool(continue_sum)),
+                             _stream(dev)), "fc_wire_fold")
+    return out
 
 
 def weighted_sum_dense(rows, weights: torch.Tensor, out: Optional[torch.Tensor] = None,
