@@ -34,6 +34,12 @@ constexpr int kShards = 64;                 // sharded k_compact totals
 constexpr uint32_t kNanKey = 0x7f800001u;   // every NaN sorts above +inf
 constexpr uint64_t kSelectNothing = 1ull << 63;
 
+// Quarter q's slots [*st, *en) from a chunk's quarter-offset word (include/fedcodec.h), unclamped.
+__device__ __forceinline__ void quarter_range(uint64_t qo, int q, uint32_t* st, uint32_t* en) {
+  *st = q == 0 ? 0u : (uint32_t)(qo >> (16 * (q - 1))) & 0xffffu;
+  *en = q == 3 ? (uint32_t)(qo >> 48) : (uint32_t)(qo >> (16 * q)) & 0xffffu;
+}
+
 template <typename T>
 __device__ __forceinline__ T ld_agent(const T* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -631,7 +631,8 @@ __global__ __launch_bounds__(kSBlock, kSBlocksPerCU) void k_decode_sparse(Decode
 
 // --------------------------------------------------------------------------------------
 // k_fold_q: the FedAVG fold of FC_FMT_IDXVAL packets (aggregation.py:61-63 + gar.py:44) with
-// quarter ownership.  One workgroup of 4 waves per chunk; wave q owns quarter q (2048 elements,
+// quarter ownership (its body, fold_body, is k_fold_wire's too: fc_wire_fold.hip, another source).
+// One workgroup of 4 waves per chunk; wave q owns quarter q (2048 elements,
 // an 8 KB LDS tile) and folds every packet's entries of that quarter in G's row order,
 //     tile[loc] = fl(tile[loc] + fl(w * v))           (__fmul_rn / __fadd_rn, no FMA)
 // with NO barrier: the quarter's entries are the slot range [qoff_q, qoff_q+1) the encoder
@@ -670,11 +671,12 @@ struct QMeta {
   uint64_t thresh;
   float w;
   uint32_t flags;                               // ib | codec << 8 | key_mode << 16 | poison << 24
-};                                              //    | kQNoQoff
+};                                              //    | kQNoQoff | kQNanDropped
 // a view without quarter offsets (the encoders may be given qoff = NULL): QMeta::qoff holds the
 // per-chunk counts instead, and the chunk's offsets word becomes kQWhole | cnt — every quarter
 // then scans the whole slot range [0, cnt) (slow body, loc filter), so the fold stays correct
 constexpr uint32_t kQNoQoff = 1u << 25;
+constexpr uint32_t kQNanDropped = 1u << 26;     // dropout-unbiased with p = 0: dropped means NaN
 constexpr uint64_t kQWhole = 1ull << 63;        // never set in real offsets (cnt <= 8192)
 
 // One entry of a packet folded into the quarter tile with the full per-entry rules (the slow
@@ -691,89 +693,138 @@ __device__ __forceinline__ void fold_q_entry(const PktCache& pk, float w, float*
 // DEC: the dense decode of ONE packet with the same quarter-owned waves (no workgroup barrier
 // per chunk): the tile starts at the packet's dropped value (+0, or NaN for dropout-unbiased
 // with p = 0) and every kept entry is ASSIGNED, tile[loc] = v (-0.0 kept), instead of folded.
-template <bool ACC_IN, bool DEC = false>
-__global__ __launch_bounds__(kQBlock, 4) void k_fold_q(DecodeArgs a) {
-  __shared__ __attribute__((aligned(16))) float tile[kChunk];
-  __shared__ QMeta s_meta[kSparseMaxM];
-  __shared__ uint32_t s_mark[4][kQuarter / 32];   // poisoning packets: kept-location bits
-  __shared__ uint32_t s_slow;
-  const int tid = threadIdx.x, lane = lane_id();
+//
+// The fold's body exists once (fold_body below) and reads its packets through a SOURCE: the
+// slotted packets of a DecodeArgs here (FoldSlots), the wire packets of fc_wire_fold.hip there.
+// A source says where a packet's record comes from (Meta; fill sets it but thresh, leaves its
+// own bits in flags and returns the packet header, nullptr: no packet), where a quarter's entries
+// are (load once per chunk, lane_count per lane, span by readlane) and seed, offset, p (rules).
+struct FoldSpan { gu16* idx; gf32* val; uint32_t lo, hi; };   // an item's entries e in [lo, hi)
+
+template <bool DEC>
+struct FoldSlots {
+  typedef QMeta Meta;
+  const DecodeArgs a;
+  const uint32_t c;                             // this workgroup's chunk, its first element below
   // wave-uniform to the compiler (tid >> 6 is not): every range derived from q stays scalar and
   // the entry loads take a scalar base + 32-bit lane offset instead of per-lane 64-bit
   // addresses (fewer VALU per entry: the fold is issue-bound, not byte-bound)
-  const int q = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const uint32_t M = (uint32_t)a.m;
-  const uint32_t c = blockIdx.x;
-  const uint64_t base = (uint64_t)c * kChunk;
-  const uint32_t qbase = (uint32_t)base + (uint32_t)(q * kQuarter);
+  const int q;
+  const uint64_t base;
+  uint64_t qo0, qo1;                            // the raw offset words: decoded after the readlane
+  __device__ __forceinline__ explicit FoldSlots(const DecodeArgs& a_)
+      : a(a_), c(blockIdx.x), q(__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)),
+        base((uint64_t)blockIdx.x * kChunk), qo0(0), qo1(0) {}
+  __device__ __forceinline__ const fc_packet_hdr* fill(int tid, QMeta& d) const {
+    const fc_packet_view v = DEC ? a.one : a.views[tid];
+    d.idx = v.idx; d.val = v.val; d.hdr = v.hdr; d.w = v.weight;
+    d.qoff = v.qoff ? (const void*)v.qoff : (const void*)v.cnt;
+    d.flags = v.qoff ? 0u : kQNoQoff;
+    return v.hdr;
+  }
+  // (a per-lane pointer: each lane reads a different packet's array)
+  __device__ __forceinline__ void load(const QMeta* s_meta, uint32_t M, int lane) {
+    typedef __attribute__((address_space(1))) const uint64_t gu64;
+    auto qload = [&](uint32_t m) -> uint64_t {
+      const QMeta& pm = s_meta[m];
+      if (pm.flags & kQNoQoff) return kQWhole | ((gu32*)pm.qoff)[c];
+      return ((gu64*)pm.qoff)[c];
+    };
+    qo0 = (uint32_t)lane < M ? qload((uint32_t)lane) : 0ull;
+    qo1 = (uint32_t)lane + 64 < M ? qload((uint32_t)lane + 64) : 0ull;
+  }
+  __device__ __forceinline__ uint32_t lane_count(bool hi) const {
+    uint32_t st, en;
+    quarter_range(hi ? qo1 : qo0, q, &st, &en);
+    return ((hi ? qo1 : qo0) & kQWhole) ? kQuarter + 1u : en - st;   // whole-chunk scan: slow body
+  }
+  __device__ __forceinline__ FoldSpan span(const QMeta& pm, uint32_t m) const {   // uniform
+    const uint64_t src = m < 64 ? qo0 : qo1;
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)src, (int)(m & 63));
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(src >> 32), (int)(m & 63));
+    const uint64_t v = ((uint64_t)hi << 32) | lo;
+    FoldSpan s;
+    quarter_range(v, q, &s.lo, &s.hi);
+    if (v & kQWhole) { s.lo = 0u; s.hi = lo & 0xffffu; }  // no qoff: the whole slot range
+    s.val = (gf32*)uni_ptr(pm.val) + base; s.idx = (gu16*)uni_ptr(pm.idx) + base;
+    return s;
+  }
+  __device__ __forceinline__ void rules(const QMeta& pm, PktCache& pk) const {
+    const fc_packet_hdr* h = (const fc_packet_hdr*)uni_ptr(pm.hdr);
+    pk.seed = h->seed; pk.offset = h->offset; pk.p = h->p;
+  }
+};
+
+template <bool ACC_IN, bool DEC, class Src>
+__device__ __forceinline__ void fold_body(Src& src, uint32_t M, float* out, uint64_t n) {
+  typedef typename Src::Meta Meta;
+  __shared__ __attribute__((aligned(16))) float tile[kChunk];
+  __shared__ Meta s_meta[kSparseMaxM];
+  __shared__ uint32_t s_mark[4][kQuarter / 32];   // poisoning packets: kept-location bits
+  __shared__ uint32_t s_slow;
+  const int tid = threadIdx.x, lane = lane_id();
+  const int q = src.q;
+  const uint32_t base = (uint32_t)src.base;         // n < 2^32
+  const uint32_t qbase = base + (uint32_t)(q * kQuarter);
   if (tid == 0) s_slow = 0;
   s_mark[q][lane] = 0u;
   __syncthreads();
   if (tid < (int)M) {
-    const fc_packet_view v = DEC ? a.one : a.views[tid];
-    const fc_packet_hdr* h = v.hdr;
-    QMeta d;
-    d.idx = v.idx; d.val = v.val; d.hdr = h;
-    d.qoff = v.qoff ? (const void*)v.qoff : (const void*)v.cnt;
-    d.thresh = h->thresh; d.w = v.weight;
-    const uint32_t codec = h->codec, key_mode = h->key_mode;
-    const float dz = (codec == FC_CODEC_DROPOUT_UNBIASED && h->p == 0.0) ? __uint_as_float(0x7fc00000u) : 0.0f;
-    const bool poison = __fmul_rn(dz, v.weight) != __fmul_rn(dz, v.weight);
+    Meta d;
+    const fc_packet_hdr* h = src.fill(tid, d);      // no packet: an empty top-k one selecting nothing
+    d.thresh = kSelectNothing;
+    uint32_t ib = 1u, codec = FC_CODEC_TOP, key_mode = FC_KEY_MAGNITUDE;
+    bool poison = false;
+    if (h != nullptr) {
+      d.thresh = h->thresh; ib = h->index_bits & 0xffu; codec = h->codec; key_mode = h->key_mode;
+      if (codec == FC_CODEC_DROPOUT_UNBIASED && h->p == 0.0) d.flags |= kQNanDropped;
+      const float dz = (d.flags & kQNanDropped) ? __uint_as_float(0x7fc00000u) : 0.0f;
+      poison = __fmul_rn(dz, d.w) != __fmul_rn(dz, d.w);
+    }
     // the fast body's float form of comp >= T64 needs T64's key below +inf bits (k = 0's
     // kSelectNothing and an inf / NaN k-th element take the per-entry rules)
     const bool generic = codec == FC_CODEC_DROPOUT_UNBIASED || (key_mode == FC_KEY_PHILOX && d.thresh != 0) ||
-                         (d.thresh >> (h->index_bits & 0xffu)) >= 0x7f800000ull;
-    d.flags = (h->index_bits & 0xffu) | ((codec & 0xffu) << 8) | ((key_mode & 0xffu) << 16) |
-              ((uint32_t)poison << 24) | (v.qoff ? 0u : kQNoQoff);
+                         (d.thresh >> ib) >= 0x7f800000ull;
+    d.flags |= ib | ((codec & 0xffu) << 8) | ((key_mode & 0xffu) << 16) | ((uint32_t)poison << 24);
     s_meta[tid] = d;
     if (poison || generic) atomicOr(&s_slow, 1u);
   }
   __syncthreads();                              // the only workgroup barriers
   const bool slow = s_slow != 0;
-  // this chunk's quarter offsets of packets lane and lane + 64
-  // (a per-lane pointer: each lane reads a different packet's array)
-  typedef __attribute__((address_space(1))) const uint64_t gu64;
-  typedef __attribute__((address_space(1))) const uint32_t gu32c;
-  auto qload = [&](uint32_t m) -> uint64_t {
-    const QMeta& pm = s_meta[m];
-    if (pm.flags & kQNoQoff) return kQWhole | ((gu32c*)pm.qoff)[c];
-    return ((gu64*)pm.qoff)[c];
+  src.load(s_meta, M, lane);
+  // a quarter holding more than kQTail * 64 entries in any packet sends this wave to the slow
+  // body too: the fast body's tail loop is for the rare longer item (a load loop inside the
+  // pipeline makes the compiler wait vmcnt(0) for the other slot's loads)
+  const bool dense_q = __any(src.lane_count(false) > (uint32_t)(kQTail * 64) ||
+                             src.lane_count(true) > (uint32_t)(kQTail * 64));
+  // the per-entry rules of a packet: thresh and the rule bits of its record, the source's rest
+  auto pkt_cache = [&](const Meta& pm) {
+    PktCache pk;
+    pk.thresh = uni64(pm.thresh); pk.ib = uni32(pm.flags) & 0xffu;
+    pk.codec = (uni32(pm.flags) >> 8) & 0xffu; pk.key_mode = (uni32(pm.flags) >> 16) & 0xffu;
+    src.rules(pm, pk);
+    return pk;
   };
-  const uint64_t qo0 = (uint32_t)lane < M ? qload((uint32_t)lane) : 0ull;
-  const uint64_t qo1 = (uint32_t)lane + 64 < M ? qload((uint32_t)lane + 64) : 0ull;
-  // a quarter holding more than kQR * 64 entries in any packet sends this wave to the slow
-  // body too: the fast body has no tail loop (a load loop inside the pipeline made the
-  // compiler wait vmcnt(0) for the other slot's loads)
-  auto qcount = [&](uint64_t v) -> uint32_t {
-    if (v & kQWhole) return kQuarter + 1u;                  // whole-chunk scan: slow body
-    const uint32_t st = q == 0 ? 0u : (uint32_t)(v >> (16 * (q - 1))) & 0xffffu;
-    const uint32_t en = q == 3 ? (uint32_t)(v >> 48) : (uint32_t)(v >> (16 * q)) & 0xffffu;
-    return en - st;
-  };
-  const bool dense_q = __any(qcount(qo0) > (uint32_t)(kQTail * 64) || qcount(qo1) > (uint32_t)(kQTail * 64));
-  auto range = [&](uint32_t m, uint32_t& st, uint32_t& en) {   // uniform
-    const uint64_t src = m < 64 ? qo0 : qo1;
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)src, (int)(m & 63));
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(src >> 32), (int)(m & 63));
-    const uint64_t v = ((uint64_t)hi << 32) | lo;
-    st = q == 0 ? 0u : (uint32_t)(v >> (16 * (q - 1))) & 0xffffu;
-    en = q == 3 ? (uint32_t)(v >> 48) : (uint32_t)(v >> (16 * q)) & 0xffffu;
-    if (v & kQWhole) { st = 0u; en = lo & 0xffffu; }      // no qoff: the whole slot range
+  // the bits of s_mark[q] of the locations packet pk keeps among the entries of s
+  auto mark_kept = [&](const PktCache& pk, const FoldSpan& s) {
+    for (uint32_t e = s.lo + lane; e < s.hi; e += 64) {
+      const uint32_t id = base + s.idx[e];
+      const uint32_t loc = id - qbase;
+      if (loc < (uint32_t)kQuarter && entry_kept(pk, id, s.val[e]))
+        atomicOr(&s_mark[q][loc >> 5], 1u << (loc & 31));
+    }
   };
   // ---- tile init: +0 (np.sum's start) or the partial sum being continued ----
   float* qt = tile + q * kQuarter;
   float dz0 = 0.f;                                  // DEC: the dropped coordinates' value
-  if (DEC) {
-    const fc_packet_hdr* h = (const fc_packet_hdr*)uni_ptr(s_meta[0].hdr);
-    if (h->codec == FC_CODEC_DROPOUT_UNBIASED && h->p == 0.0) dz0 = __uint_as_float(0x7fc00000u);
-  }
+  if (DEC && (uni32(s_meta[0].flags) & kQNanDropped)) dz0 = __uint_as_float(0x7fc00000u);
   bool nz = false;                                  // ACC_IN: the sum to continue holds a -0.0
 #pragma unroll
   for (int i = 0; i < kQuarter / 256; ++i) {
     const uint32_t loc = (uint32_t)(i * 256 + lane * 4);
     float4 v = make_float4(dz0, dz0, dz0, dz0);
     if (ACC_IN) {
-      v = load4(reinterpret_cast<const float*>(a.out), (uint64_t)qbase + loc, a.n);
+      v = load4(out, (uint64_t)qbase + loc, n);
       nz |= (__float_as_uint(v.x) == 0x80000000u) | (__float_as_uint(v.y) == 0x80000000u) |
             (__float_as_uint(v.z) == 0x80000000u) | (__float_as_uint(v.w) == 0x80000000u);
     }
@@ -782,34 +833,22 @@ __global__ __launch_bounds__(kQBlock, 4) void k_fold_q(DecodeArgs a) {
   const bool neg0_in = ACC_IN && __any(nz);         // wave-uniform; never true for a sum a fold made
   if (slow || dense_q) {
     // ---- slow body (a launch holding rand-k Philox, dropout-unbiased or NaN-poisoning
-    // packets, or a quarter with more than kQR * 64 entries): item by item, every rule per
+    // packets, or a quarter with more than kQTail * 64 entries): item by item, every rule per
     // entry ----
     for (uint32_t m = 0; m < M; ++m) {
-      uint32_t st, en;
-      range(m, st, en);
-      const QMeta& pm = s_meta[m];
-      const fc_packet_hdr* h = (const fc_packet_hdr*)uni_ptr(pm.hdr);
-      PktCache pk;
-      pk.thresh = uni64(pm.thresh); pk.ib = uni32(pm.flags) & 0xffu;
-      pk.codec = (uni32(pm.flags) >> 8) & 0xffu; pk.key_mode = (uni32(pm.flags) >> 16) & 0xffu;
-      pk.seed = h->seed; pk.offset = h->offset; pk.p = h->p;
+      const Meta& pm = s_meta[m];
+      const FoldSpan s = src.span(pm, m);
+      const PktCache pk = pkt_cache(pm);
       const float w = __uint_as_float(uni32(__float_as_uint(pm.w)));
-      gu16* pidx = (gu16*)uni_ptr(pm.idx) + base;
-      gf32* pval = (gf32*)uni_ptr(pm.val) + base;
       if (!DEC && ((uni32(pm.flags) >> 24) & 1u)) {   // poisoning: NaN where this packet folds nothing
-        for (uint32_t e = st + lane; e < en; e += 64) {
-          const uint32_t id = (uint32_t)base + pidx[e];
-          const uint32_t loc = id - qbase;
-          if (loc < (uint32_t)kQuarter && entry_kept(pk, id, pval[e]))
-            atomicOr(&s_mark[q][loc >> 5], 1u << (loc & 31));
-        }
+        mark_kept(pk, s);
         const uint32_t bits = s_mark[q][lane];
         for (int b = 0; b < 32; ++b)
           if (!((bits >> b) & 1u)) qt[lane * 32 + b] = __uint_as_float(0x7fc00000u);
         s_mark[q][lane] = 0u;
       }
-      for (uint32_t e = st + lane; e < en; e += 64)
-        fold_q_entry<DEC>(pk, w, qt, qbase, (uint32_t)base + pidx[e], pval[e]);
+      for (uint32_t e = s.lo + lane; e < s.hi; e += 64)
+        fold_q_entry<DEC>(pk, w, qt, qbase, base + s.idx[e], s.val[e]);
     }
   } else {
     // ---- fast body: top-k / mask-selected packets; two register slots of kQGroup items, the
@@ -831,15 +870,15 @@ __global__ __launch_bounds__(kQBlock, 4) void k_fold_q(DecodeArgs a) {
 #pragma unroll
       for (int d = 0; d < kQGroup; ++d) {
         const uint32_t m = min(m0 + (uint32_t)d, M - 1);          // past the end: re-load (ignored)
-        uint32_t st, en;
-        range(m, st, en);
-        qn_[sl][d] = en - st;
-        const QMeta& pm = s_meta[m];
-        gf32* val = (gf32*)uni_ptr(pm.val) + base + st;
-        gu16* idx = (gu16*)uni_ptr(pm.idx) + base + st;
+        // the loads stay unconditional (a branch around them would make the compiler wait for the
+        // other slot's loads too): entry lo of a span with no entries may be read (ignored: lim <= 0)
+        const FoldSpan s = src.span(s_meta[m], m);
+        qn_[sl][d] = s.hi - s.lo;
+        gf32* val = s.val + s.lo;
+        gu16* idx = s.idx + s.lo;
         // lanes past the item's end re-read its last entry (one address, no extra traffic:
         // unclamped loads of the next entries cost +25 % bytes, 19.4 against 17.6 us/packet)
-        const uint32_t last = en > st ? en - st - 1u : 0u;
+        const uint32_t last = s.hi > s.lo ? s.hi - s.lo - 1u : 0u;
 #pragma unroll
         for (int r = 0; r < kQR; ++r) {
           const uint32_t e = min((uint32_t)(lane + r * 64), last);
@@ -853,14 +892,13 @@ __global__ __launch_bounds__(kQBlock, 4) void k_fold_q(DecodeArgs a) {
       for (int d = 0; d < kQGroup; ++d) {
         const uint32_t m = m0 + (uint32_t)d;
         if (m >= M) break;                                        // uniform
-        const QMeta& pm = s_meta[m];
+        const Meta& pm = s_meta[m];
         const float w = __uint_as_float(uni32(__float_as_uint(pm.w)));
         const uint64_t thresh = uni64(pm.thresh);
         const uint32_t ib = uni32(pm.flags) & 0xffu;
         const float Tf = __uint_as_float((uint32_t)(thresh >> ib));
         const uint32_t Ti = (uint32_t)(thresh & ((1ull << ib) - 1ull));
-        const uint32_t b32 = (uint32_t)base;
-        const uint32_t Tr = Ti <= b32 ? 0u : min(Ti - b32, (uint32_t)kChunk);   // tie cut in the chunk
+        const uint32_t Tr = Ti <= base ? 0u : min(Ti - base, (uint32_t)kChunk);   // tie cut in the chunk
         const uint32_t qn = qn_[sl][d];
         const int lim = (int)qn - lane;                           // entries left for this lane
         // branch-free: a lane whose entry is not folded (past the item's end, or slack below
@@ -882,13 +920,10 @@ __global__ __launch_bounds__(kQBlock, 4) void k_fold_q(DecodeArgs a) {
         for (int r = 0; r < kQR; ++r)
           *slot[r] = DEC ? vs_[sl][d][r] : __fadd_rn(tv[r], __fmul_rn(vs_[sl][d][r], w));
         if (kQTail > kQR && qn > (uint32_t)(kQR * 64)) {          // rare, uniform: the rest
-          uint32_t st, en;
-          range(m, st, en);
-          gf32* val = (gf32*)uni_ptr(pm.val) + base;
-          gu16* idx = (gu16*)uni_ptr(pm.idx) + base;
-          for (uint32_t e = st + (uint32_t)(kQR * 64) + lane; e < en; e += 64) {
-            const uint32_t lc = idx[e];
-            const float v = val[e];
+          const FoldSpan s = src.span(pm, m);
+          for (uint32_t e = s.lo + (uint32_t)(kQR * 64) + lane; e < s.hi; e += 64) {
+            const uint32_t lc = s.idx[e];
+            const float v = s.val[e];
             const float av = __builtin_fabsf(v);
             const uint32_t l2 = lc & (uint32_t)(kQuarter - 1);
             if (!(av <= Tf) | ((av == Tf) & (lc >= Tr)))
@@ -914,25 +949,12 @@ __global__ __launch_bounds__(kQBlock, 4) void k_fold_q(DecodeArgs a) {
     // no packet with a sign-positive weight dropped it: mark what each such packet keeps and
     // turn the unmarked -0.0 into +0 ----
     for (uint32_t m = 0; m < M; ++m) {
-      const QMeta& pm = s_meta[m];
+      const Meta& pm = s_meta[m];
       const float w = __uint_as_float(uni32(__float_as_uint(pm.w)));
       if (__float_as_uint(w) >> 31) continue;       // fl(+0 * w) = -0: skipping it was exact
-      uint32_t st, en;
-      range(m, st, en);
-      const fc_packet_hdr* h = (const fc_packet_hdr*)uni_ptr(pm.hdr);
-      PktCache pk;
-      pk.thresh = uni64(pm.thresh); pk.ib = uni32(pm.flags) & 0xffu;
-      pk.codec = (uni32(pm.flags) >> 8) & 0xffu; pk.key_mode = (uni32(pm.flags) >> 16) & 0xffu;
-      pk.seed = h->seed; pk.offset = h->offset; pk.p = h->p;
-      gu16* pidx = (gu16*)uni_ptr(pm.idx) + base;
-      gf32* pval = (gf32*)uni_ptr(pm.val) + base;
+      const PktCache pk = pkt_cache(pm);
       s_mark[q][lane] = 0u;                         // (the fast body's dummy slots)
-      for (uint32_t e = st + lane; e < en; e += 64) {
-        const uint32_t id = (uint32_t)base + pidx[e];
-        const uint32_t loc = id - qbase;
-        if (loc < (uint32_t)kQuarter && entry_kept(pk, id, pval[e]))
-          atomicOr(&s_mark[q][loc >> 5], 1u << (loc & 31));
-      }
+      mark_kept(pk, src.span(pm, m));
       const uint32_t bits = s_mark[q][lane];
       for (int b = 0; b < 32; ++b)
         if (!((bits >> b) & 1u) && __float_as_uint(qt[lane * 32 + b]) == 0x80000000u)
@@ -941,12 +963,17 @@ __global__ __launch_bounds__(kQBlock, 4) void k_fold_q(DecodeArgs a) {
     }
   }
   // ---- write the quarter out ----
-  float* out = reinterpret_cast<float*>(a.out);
 #pragma unroll
   for (int i = 0; i < kQuarter / 256; ++i) {
     const uint32_t loc = (uint32_t)(i * 256 + lane * 4);
-    store_out(out, (uint64_t)qbase + loc, a.n, *reinterpret_cast<const float4*>(&qt[loc]));
+    store_out(out, (uint64_t)qbase + loc, n, *reinterpret_cast<const float4*>(&qt[loc]));
   }
+}
+
+template <bool ACC_IN, bool DEC = false>
+__global__ __launch_bounds__(kQBlock, 4) void k_fold_q(DecodeArgs a) {
+  FoldSlots<DEC> src(a);
+  fold_body<ACC_IN, DEC>(src, (uint32_t)a.m, reinterpret_cast<float*>(a.out), a.n);
 }
 
 // --------------------------------------------------------------------------------------
@@ -1002,8 +1029,8 @@ __global__ __launch_bounds__(kQBlock, 4) void k_decode_res(DecResArgs a) {
   __builtin_amdgcn_wave_barrier();
   bool finisher = false;
   if (!(flags & 1u)) {
-    const uint32_t st = q == 0 ? 0u : (uint32_t)(qo >> (16 * (q - 1))) & 0xffffu;
-    const uint32_t en = q == 3 ? (uint32_t)(qo >> 48) : (uint32_t)(qo >> (16 * q)) & 0xffffu;
+    uint32_t st, en;
+    quarter_range(qo, q, &st, &en);
     gu16* pidx = (gu16*)a.idx + base;
     gf32* pval = (gf32*)a.val + base;
     for (uint32_t e = st + (uint32_t)lane; e < en; e += 64) {

@@ -126,8 +126,8 @@ __device__ __forceinline__ bool gram_value(const GramRule& r, uint64_t base, uin
 }
 
 __device__ __forceinline__ void gram_range(uint64_t qo, int q, uint32_t* st, uint32_t* en) {
-  uint32_t s = q == 0 ? 0u : (uint32_t)(qo >> (16 * (q - 1))) & 0xffffu;
-  uint32_t e = q == 3 ? (uint32_t)(qo >> 48) : (uint32_t)(qo >> (16 * q)) & 0xffffu;
+  uint32_t s, e;
+  quarter_range(qo, q, &s, &e);
   e = min(e, (uint32_t)kChunk);                   // never outside the chunk's slot
   *st = min(s, e); *en = e;
 }

@@ -22,9 +22,9 @@
 // kernel checked total_bytes against; entry positions are checked against E on top of that.
 //
 // Unpack, one wave per (client, chunk): k_wire_unpack reads start[c] and the chunk's word, clamps
-// them against E and each other, and copies the entries to the chunk's slot.  Whatever the bytes
-// hold, every read is below the byte length the host passed (the sections are laid out from n and
-// E, and a packet whose E does not fit the length is unpacked as an empty packet with status
+// them (wire_accept, wire_clamp of fc_wire_host.h) and copies the entries to its slot.  Whatever the
+// bytes hold, every read is below the byte length the host passed (the sections are laid out from
+// n and E, and a packet whose E does not fit the length is unpacked as an empty packet with status
 // FC_STATUS_OVERFLOW) and every write lands inside [c*8192, c*8192 + 8192) of the destination.
 #include "fc_state.h"
 #include "fc_wire_host.h"
@@ -222,9 +222,7 @@ __global__ __launch_bounds__(kWBlock) void k_wire_unpack(WireArgs a) {
     const fc_wire_hdr* h = reinterpret_cast<const fc_wire_hdr*>(wire);
     E = uni64(h->n_entries);
     wstatus = uni32(h->status);
-    valid = uni32(h->magic) == kWireMagic && uni32(h->version) == kWireVersion &&
-            uni32(h->nch) == a.nch && (uint64_t)uni32(h->pkt.n) == a.n && E <= 0xffffffffull &&
-            wire_layout(a.n, E).total <= bytes;
+    valid = wire_accept(h, a.n, a.nch, bytes, E, [](uint32_t x) { return uni32(x); });   // uniform words
     if (!valid) E = 0;
   }
   if (c == 0 && lane < (int)(sizeof(fc_packet_hdr) / 4)) {    // the header, one 32-bit word per lane
@@ -252,11 +250,8 @@ __global__ __launch_bounds__(kWBlock) void k_wire_unpack(WireArgs a) {
   if (valid) {
     const WireLayout L = wire_layout(a.n, E);
     const uint64_t qo = reinterpret_cast<const uint64_t*>(wire + L.off_qoff)[c];
-    st = min((uint64_t)reinterpret_cast<const uint32_t*>(wire + L.off_start)[c], E);
-    cnt = (uint32_t)min((uint64_t)min((uint32_t)(qo >> 48), (uint32_t)kChunk), E - st);
-    q3 = min((uint32_t)(qo >> 32) & 0xffffu, cnt);
-    q2 = min((uint32_t)(qo >> 16) & 0xffffu, q3);
-    q1 = min((uint32_t)qo & 0xffffu, q2);
+    const WireChunk<uint64_t> k = wire_clamp(qo, reinterpret_cast<const uint32_t*>(wire + L.off_start)[c], E);
+    st = k.st; cnt = k.cnt; q3 = k.q3; q2 = k.q2; q1 = k.q1;
     // entries [st, st + cnt) are below E: inside the idx and val sections, so inside `bytes`
     const uint16_t* sidx = reinterpret_cast<const uint16_t*>(wire + L.off_idx) + st;
     const uint32_t* sval = reinterpret_cast<const uint32_t*>(wire + L.off_val) + st;

@@ -1,6 +1,8 @@
-// fc_wire_host.h — the wire format of an FC_FMT_IDXVAL packet: layout, size and the host
-// validator.  Plain C++17 with no HIP includes, so a host compiler takes it alone
-// (tests/wire_validate_main.cc); fc_wire.hip includes it for the same layout on the device.
+// fc_wire_host.h — the wire format of an FC_FMT_IDXVAL packet: layout, size, the host validator
+// and the two rules of the device readers that take unvalidated bytes (wire_accept, wire_clamp).
+// Plain C++17 with no HIP includes, so a host compiler takes it alone
+// (tests/wire_validate_main.cc); fc_wire.hip includes it for the same layout and rules on the
+// device.
 //
 // One packet is one contiguous little-endian byte string; every section starts 16-B aligned and
 // pad bytes are zero:
@@ -58,6 +60,39 @@ FC_WIRE_HD inline WireLayout wire_layout(uint64_t n, uint64_t E) {
   L.off_val = L.off_idx + wire_pad16(2 * E);
   L.total = L.off_val + wire_pad16(4 * E);
   return L;
+}
+
+// ---- what a device reader (k_wire_unpack, the wire fold) does with bytes nobody validated ----
+// Is the buffer behind header h (bytes >= 128: the caller checks that first) a packet of the
+// caller's n and nch inside `bytes`?  E is h->n_entries as the caller read it, once.  Accepted:
+// both tables and entries [0, E) of idx and val lie below `bytes`.  u is applied to every header
+// word as it is read (k_wire_unpack makes them wave-uniform); no other word is read.
+template <typename U>
+FC_WIRE_HD inline bool wire_accept(const fc_wire_hdr* h, uint64_t n, uint32_t nch, uint64_t bytes,
+                                   uint64_t E, U u) {
+  return u(h->magic) == kWireMagic && u(h->version) == kWireVersion && u(h->nch) == nch &&
+         (uint64_t)u(h->pkt.n) == n && E <= 0xffffffffull && wire_layout(n, E).total <= bytes;
+}
+
+// Chunk c's entries [st, st + cnt) and its quarter boundaries 0 <= q1 <= q2 <= q3 <= cnt from the
+// chunk's offsets word and start word, clamped: st + cnt <= E and cnt <= 8192 whatever the words
+// hold; a payload wire_validate accepts comes back as stored.  T: the width E (< 2^32) is held in.
+template <typename T>
+struct WireChunk {
+  T st;
+  uint32_t q1, q2, q3, cnt;
+};
+template <typename T>
+FC_WIRE_HD inline T wire_min(T a, T b) { return a < b ? a : b; }
+template <typename T>
+FC_WIRE_HD inline WireChunk<T> wire_clamp(uint64_t qo, uint32_t start, T E) {
+  WireChunk<T> k;
+  k.st = wire_min<T>(start, E);
+  k.cnt = (uint32_t)wire_min<T>(wire_min<uint32_t>((uint32_t)(qo >> 48), (uint32_t)kWireChunk), E - k.st);
+  k.q3 = wire_min<uint32_t>((uint32_t)(qo >> 32) & 0xffffu, k.cnt);
+  k.q2 = wire_min<uint32_t>((uint32_t)(qo >> 16) & 0xffffu, k.q3);
+  k.q1 = wire_min<uint32_t>((uint32_t)qo & 0xffffu, k.q2);
+  return k;
 }
 
 inline uint32_t wire_index_bits(uint64_t n) {

@@ -9,7 +9,8 @@ tests/wire_model.py's unpack of the same bytes; the second witness is the route 
 codec.decode_accumulate(codec.unpack(wires), ...).  Everything is compared bit for bit
 (po.same_bits).  Only well-formed payloads reach the GPU, each through codec.wire_from_host.
 
-Switch points of the kernel (names of csrc/fc_decode.hip / fc_wire_fold.hip, not imported):
+Switch points of the kernel (names of csrc/fc_decode.hip, whose fold_body both folds run; not
+imported):
   64 lanes            quarter counts 63, 64, 65
   kQR * 64 = 256      entries per item of the fast body: 255, 256, 257
   kQTail * 64 = 512   above it the wave takes the slow body: 513 listed, ~360 kept (tail), 2048
@@ -155,6 +156,34 @@ def test_top_k_only_takes_the_fast_body_and_its_tail():
     w = np.float32([0.5, 0.75, 1.25, 3.0, 1.0 / 3])
     codec.fold_wire(upload(payloads, N), [float(x) for x in w], out=out, continue_sum=True)
     assert po.same_bits(host(out), expected(payloads, w, acc))
+
+
+# ---- 2b. packets that keep nothing ---------------------------------------------------------------
+def keeps_nothing(thresh):
+    return wm.pack(po.build_idxval(N, np.zeros(0, np.int64), np.zeros(0, np.float32), thresh=thresh,
+                                   codec=po.CODEC_TOP, k=0))
+
+
+@pytest.mark.parametrize("thresh", ["select-nothing", "finite"])
+def test_packets_with_no_entries_beside_ordinary_top_k(thresh):
+    """M = 4: packets 0 and 3 keep nothing (E = 0), 1 and 2 are ordinary top-k.  With kQGroup = 3
+    the load groups are (0, 1, 2) and (3, 3, 3): an item with no entries is first in a group, last in
+    a group, in the past-the-end reload slots, and a packet of its own, so the fast body's
+    unconditional loads of it read the first weight and no byte of its buffer.  A select-nothing
+    thresh sends the whole launch to the slow body (its key is above +inf bits); the same round
+    under a finite thresh is the one whose waves take the fast body: that needs the whole launch
+    non-generic, which the two top-k payloads are (test_top_k_only_... asserts it of them)."""
+    ib = po.index_bits(N)
+    T = int(po.NOTHING) if thresh == "select-nothing" else int(po.mag_key(np.array([twg.TIE]))[0]) << ib
+    empty = keeps_nothing(T)
+    h = wm.parse(empty)["hdr"]
+    assert int(h["n_entries"]) == 0 and int(h["pkt"]["thresh"]) == T
+    assert ((T >> ib) < 0x7F800000) == (thresh == "finite")
+    tops = top_payloads()
+    payloads = [empty, tops[0], tops[1], empty]
+    per = np.stack([quarter_counts(raw) for raw in payloads]).max(axis=0)
+    assert (per <= 512).any()                                        # waves that may take the fast body
+    check_round(payloads, np.float32([0.5, -0.75, 1.25, 3.0]), N, seed=11)
 
 
 # ---- 3. the keep rule on wire bytes --------------------------------------------------------------

@@ -276,3 +276,39 @@ def test_the_corpus_through_the_sanitized_standalone_program(lib, standalone, tm
         else:
             assert got.startswith("BAD wire: ") and re.search(want, got), f"{name}: {got}"
     print(f"{len(corpus)} payloads, sanitized build: {sanitized}")
+
+
+def test_the_readers_rules_on_the_corpus_through_the_sanitized_program(lib, standalone, tmp_path):
+    """wire_accept and wire_clamp (fc_wire_host.h: what k_wire_unpack and the wire fold do with bytes
+    nobody validated) on the same corpus, each payload in a heap block of exactly its length: the
+    program reads every entry of every clamped range and fails if one leaves [0, E)."""
+    exe, sanitized = standalone
+    corpus = [(name, raw, n) for name, (raw, n) in sorted(accepted_payloads().items())]
+    corpus += [(name, mutations()[name][0], mutations()[name][1] or N) for name in MUTATIONS]
+    lines = []
+    for i, (_, raw, n) in enumerate(corpus):
+        path = tmp_path / f"payload_{i:03d}.bin"
+        path.write_bytes(raw)
+        lines.append(f"{n} {path}")
+    (tmp_path / "list.txt").write_text("\n".join(lines) + "\n")
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe, "--clamp", str(tmp_path / "list.txt")], capture_output=True, text=True, env=env)
+    assert r.returncode == 0, r.stderr[-4000:]
+    assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
+    got = dict(zip((name for name, _, _ in corpus), r.stdout.splitlines()))
+    assert len(r.stdout.splitlines()) == len(corpus)
+    for name, raw, n in corpus:
+        # every payload: refused, or ranges inside [0, E) (the program checked them and read them)
+        assert got[name] == "REJECT" or re.fullmatch(r"ACCEPT E=\d+ exact=[01]", got[name]), (name, got[name])
+        if validate(lib, raw, n)[0] == 0:                           # a valid payload: the stored words
+            E = int(wm.parse(raw)["hdr"]["n_entries"])
+            assert got[name] == f"ACCEPT E={E} exact=1", (name, got[name])
+    for name in ("shorter than the header", "truncated by one byte", "wrong magic", "wrong version",
+                 "wrong nch", "n = 0", "n_expected mismatch", "E huge"):
+        assert got[name] == "REJECT", (name, got[name])
+    # a table word the readers take and bend into the packet
+    for name in ("cnt = 8193", "q2 below q1"):
+        assert got[name].endswith("exact=0"), (name, got[name])
+    for name in ("a wrong start word", "start[0] not zero", "one extra byte"):
+        assert got[name].startswith("ACCEPT"), (name, got[name])
+    print(f"{len(corpus)} payloads, sanitized build: {sanitized}")

@@ -1,10 +1,18 @@
-// Stand-alone driver of the wire validator (openmsftl_amd/csrc/fc_wire_host.h), for a host
-// compiler with -fsanitize=address,undefined (tests/test_wire_host.py builds and runs it).
+// Stand-alone driver of the wire format's host-side rules (openmsftl_amd/csrc/fc_wire_host.h), for
+// a host compiler with -fsanitize=address,undefined (tests/test_wire_host.py builds and runs it).
 //
 //   wire_validate_main LIST
 // LIST: one "n_expected path" per line.  Each payload is read into a heap block of exactly its
 // size, so a read past `len` lands in a redzone.  Prints one verdict line per payload:
 // "OK" or "BAD <reason>".
+//
+//   wire_validate_main --clamp LIST
+// LIST: one "n path" per line, n the length the reader expects.  The payload, again in a heap
+// block of exactly its size, goes through what the device readers (k_wire_unpack, the wire fold)
+// do with bytes nobody validated: wire_accept, then for every chunk wire_clamp and a read of every
+// idx and val entry of [st, st + cnt) through the section offsets.  Prints "REJECT", or
+// "ACCEPT E=<entries> exact=<1 if every chunk's clamp returned the stored words, else 0>"; exits
+// with 1 if a clamped range leaves [0, E) or its boundaries are out of order.
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -14,14 +22,62 @@
 
 #include "../openmsftl_amd/csrc/fc_wire_host.h"
 
+static volatile unsigned long long g_sink;
+
+// The readers' path over one buffer; false: a range left [0, E).
+static bool clamp_walk(const unsigned char* data, size_t size, unsigned long long n) {
+  const uint32_t nch = (uint32_t)((n + fc::kWireChunk - 1) / fc::kWireChunk);
+  if (size < fc::kWireHdrBytes) {                   // the header is not read at all
+    printf("REJECT\n");
+    return true;
+  }
+  const fc::fc_wire_hdr* h = reinterpret_cast<const fc::fc_wire_hdr*>(data);
+  const uint64_t E = h->n_entries;
+  if (!fc::wire_accept(h, n, nch, size, E, [](uint32_t x) { return x; })) {
+    printf("REJECT\n");
+    return true;
+  }
+  const fc::WireLayout L = fc::wire_layout(n, E);
+  const uint64_t* qoff = reinterpret_cast<const uint64_t*>(data + L.off_qoff);
+  const uint32_t* start = reinterpret_cast<const uint32_t*>(data + L.off_start);
+  const uint16_t* idx = reinterpret_cast<const uint16_t*>(data + L.off_idx);
+  const uint32_t* val = reinterpret_cast<const uint32_t*>(data + L.off_val);
+  bool exact = true;
+  unsigned long long sum = 0;                       // keeps the entry reads alive
+  for (uint32_t c = 0; c < nch; ++c) {
+    const uint64_t qo = qoff[c];
+    const uint32_t st0 = start[c];
+    // both widths the readers use must agree
+    const fc::WireChunk<uint32_t> k = fc::wire_clamp<uint32_t>(qo, st0, (uint32_t)E);
+    const fc::WireChunk<uint64_t> k64 = fc::wire_clamp<uint64_t>(qo, st0, E);
+    if (k64.st != k.st || k64.cnt != k.cnt || k64.q1 != k.q1 || k64.q2 != k.q2 || k64.q3 != k.q3) {
+      fprintf(stderr, "chunk %u: the 32-bit and 64-bit clamps differ\n", c);
+      return false;
+    }
+    if (!(k.q1 <= k.q2 && k.q2 <= k.q3 && k.q3 <= k.cnt && k.cnt <= FC_CHUNK && k.st <= E &&
+          (uint64_t)k.st + k.cnt <= E)) {
+      fprintf(stderr, "chunk %u: st %u q %u %u %u cnt %u leaves [0, %llu)\n", c, k.st, k.q1, k.q2, k.q3,
+              k.cnt, (unsigned long long)E);
+      return false;
+    }
+    exact = exact && k.st == st0 &&
+            qo == ((uint64_t)k.q1 | ((uint64_t)k.q2 << 16) | ((uint64_t)k.q3 << 32) | ((uint64_t)k.cnt << 48));
+    for (uint32_t e = k.st; e < k.st + k.cnt; ++e) sum += idx[e] + (unsigned long long)val[e];
+  }
+  g_sink = sum;
+  printf("ACCEPT E=%llu exact=%d\n", (unsigned long long)E, exact ? 1 : 0);
+  return true;
+}
+
 int main(int argc, char** argv) {
-  if (argc != 2) {
-    fprintf(stderr, "usage: %s LIST\n", argv[0]);
+  const bool clamp = argc == 3 && std::string(argv[1]) == "--clamp";
+  if (argc != 2 && !clamp) {
+    fprintf(stderr, "usage: %s [--clamp] LIST\n", argv[0]);
     return 2;
   }
-  std::ifstream list(argv[1]);
+  std::ifstream list(argv[argc - 1]);
   if (!list) {
-    fprintf(stderr, "cannot open %s\n", argv[1]);
+    fprintf(stderr, "cannot open %s\n", argv[argc - 1]);
     return 2;
   }
   std::string line;
@@ -40,18 +96,24 @@ int main(int argc, char** argv) {
     fseek(f, 0, SEEK_END);
     const long size = ftell(f);
     fseek(f, 0, SEEK_SET);
-    // one byte in front keeps the payload off malloc's alignment: the validator may not assume any
-    unsigned char* block = static_cast<unsigned char*>(malloc((size_t)size + 1));
-    unsigned char* data = block + 1;
+    // the validator: one byte in front keeps the payload off malloc's alignment, it may not assume
+    // any.  The readers' path: the block's own alignment, as a device buffer has it.
+    const size_t front = clamp ? 0 : 1;
+    unsigned char* block = static_cast<unsigned char*>(malloc((size_t)size + front));
+    unsigned char* data = block + front;
     if (size > 0 && fread(data, 1, (size_t)size, f) != (size_t)size) {
       fprintf(stderr, "short read of %s\n", path.c_str());
       return 2;
     }
     fclose(f);
-    char err[512] = "";
-    const int rc = fc::wire_validate(data, (size_t)size, n_expected, err, sizeof err);
-    if (rc == FC_OK) printf("OK\n");
-    else printf("BAD %s\n", err);
+    if (clamp) {
+      if (!clamp_walk(data, (size_t)size, n_expected)) return 1;
+    } else {
+      char err[512] = "";
+      const int rc = fc::wire_validate(data, (size_t)size, n_expected, err, sizeof err);
+      if (rc == FC_OK) printf("OK\n");
+      else printf("BAD %s\n", err);
+    }
     free(block);
   }
   return 0;
