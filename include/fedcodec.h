@@ -359,6 +359,36 @@ int fc_packets_dot(const fc_packet_view* views_dev, int m, uint64_t n,
                    double* out /* DEVICE float64[m + 1], 16-B aligned */,
                    void* ws, size_t ws_bytes, fc_stream_t stream);
 
+/* ---- Coordinate-wise trimmed mean (and median) of a round's packets, without the dense G ----
+ * The coordinate-wise robust rules (Yin, Chen, Ramchandran, Bartlett, ICML 2018) computed
+ * straight from the packets (fc_trim.hip).
+ * views_dev: DEVICE array of m FC_FMT_IDXVAL views with qoff present, as fc_packets_gram takes
+ *   them; `weight` is ignored.  1 <= m <= FC_GRAM_MAX_M.
+ * d_i: exactly the row fc_packets_gram uses (the same kept-entry rule: composite >= T64, the
+ *   Philox key for native rand-k, thresh == 0 keeps all, slack entries do not count;
+ *   dropout-unbiased values are fl32(fl64(v) / p)); a coordinate without a kept entry is +0.0.
+ * trim: b, the values dropped at each end of a column.  0 <= b, 2 b < m.  b = (m - 1) / 2 is the
+ *   coordinate-wise median (the float32 mean of the two middle values for even m).
+ * out[t], t < n (DEVICE float32[n], 16-B aligned): the m values d_0[t] .. d_{m-1}[t] in
+ *   np.sort's order (-inf first, -0.0 and +0.0 equal, +inf after every finite value, every NaN
+ *   after +inf); the b smallest and the b largest dropped; the other m - 2b added in ascending
+ *   order from +0.0, every add rounded to float32 (no contraction, no reassociation); the sum
+ *   divided by float32(m - 2b) in IEEE float32.  A function of the multiset of a column's values
+ *   alone: the order of the clients does not change a bit.  A column of zeros of either sign
+ *   gives +0.0.  A NaN is trimmed like a largest value: out[t] is NaN only if more than b values
+ *   are NaN or +inf and -inf both survive.  No client is excluded as a whole.
+ * One launch, one workgroup per chunk of n.  No floating-point atomics, no workgroup waits for
+ *   another (no fc_fused_order_* handling).  Two calls on the same packets give the same bits.
+ * Stream-ordered; no allocation, no host synchronisation.  ws: fc_trim_workspace_bytes(n, m)
+ *   bytes, 16-B aligned, NO one-time zeroing; the size is 0 today and ws may then be NULL.
+ * Argument errors return before the GPU is touched: FC_ERR_ARG for a NULL views_dev or out (or
+ *   ws when the size is not 0), m < 1 or m > FC_GRAM_MAX_M, trim < 0, 2 trim >= m, n == 0 (or
+ *   n >= 2^32), an out or ws that is not 16-B aligned; FC_ERR_WORKSPACE for a short workspace. */
+size_t fc_trim_workspace_bytes(uint64_t n, int m);          /* may be 0 */
+int fc_packets_trim(const fc_packet_view* views_dev, int m, uint64_t n, int trim,
+                    float* out /* DEVICE float32[n], 16-B aligned */,
+                    void* ws, size_t ws_bytes, fc_stream_t stream);
+
 /* ---- The wire form of FC_FMT_IDXVAL packets: pack, unpack, validate (fc_wire.hip) -----------
  * A slotted packet reserves 6n + 12 nch + 96 bytes whatever it keeps.  Its wire form is ONE
  * contiguous byte string that holds the kept entries alone: what a client sends.  Little-endian,

@@ -128,6 +128,8 @@ SIGNATURES = {
     "fc_packets_gram": (_i32, [_vp, _i32, _u64, _vp, _vp, _sz, _vp]),
     "fc_dot_workspace_bytes": (_sz, [_u64, _i32]),
     "fc_packets_dot": (_i32, [_vp, _i32, _u64, _vp, _vp, _vp, _sz, _vp]),
+    "fc_trim_workspace_bytes": (_sz, [_u64, _i32]),
+    "fc_packets_trim": (_i32, [_vp, _i32, _u64, _i32, _vp, _vp, _sz, _vp]),
     "fc_wire_bytes": (_u64, [_u64, _u64]),
     "fc_wire_workspace_bytes": (_sz, [_u64, _i32]),
     "fc_wire_pack_batch": (_i32, [_vp, _vp, _i32, _u64, _vp, _sz, _vp]),

@@ -48,6 +48,10 @@ GAR (gar.py:44).  Here the rows never become a dense matrix on the common path:
   ``codec.dot_dense`` for row sums or a carried vector), then the row-order fold of the packets
   with those coefficients.  ``"fed_spectral_avg"`` (the reference's class, with its autoencoder
   branch) keeps raising.
+* ``aggregation_scheme: "trimmed_mean"`` / ``"coordinate_median"`` (gar.CoordinateTrim) take the
+  same route under the same conditions: one kernel over the resident packets
+  (``codec.trimmed_mean``), unweighted (``gradient_weights`` must be None).  The rule needs no
+  Gram matrix: it is computed only when ``pc_analysis: "gram"`` asks for the singular values.
 
 * ``Aggregator.aggregate_wire(payloads)`` (:func:`aggregate_wire`) aggregates a round from the
   clients' wire packets (``Compression.compress_wire``; include/fedcodec.h) instead of their
@@ -77,8 +81,8 @@ import torch
 from . import _lib as L
 from . import codec
 from .compression import Compression, bitmask_words, kept_count
-from .gar import (CenteredClip, FedAvg, GeometricMedian, Krum, LinearRule, SpectralGram,
-                  gram_singular_values)
+from .gar import (CenteredClip, CoordinateMedian, CoordinateTrim, FedAvg, GeometricMedian, Krum,
+                  LinearRule, SpectralGram, TrimmedMean, gram_singular_values)
 from .pipeline import HostFedAvg, MtRedraw, RowCodec, RowPlan
 
 
@@ -501,28 +505,37 @@ def ef_batch_fold(agg, clients, n: int, k: int, weights: np.ndarray, dev: torch.
 
 #: the rules that are linear in the rows of G (gar.LinearRule): the "gram" route's other GARs
 _LINEAR_RULES = (SpectralGram, GeometricMedian, CenteredClip)
+#: the coordinate-wise rules (gar.CoordinateTrim): the same route, no Gram matrix needed
+_COORD_RULES = (TrimmedMean, CoordinateMedian)
 
 
 def gram_wanted(agg) -> bool:
     """Does this round take the "gram" route: the device Krum, a linear rule (spectral_gram,
-    geometric_median, centered_clip), or the device FedAvg with
+    geometric_median, centered_clip), a coordinate-wise rule (trimmed_mean, coordinate_median),
+    or the device FedAvg with
     ``pc_analysis: "gram"`` (a patched reference class keeps its own routing)."""
     gar = getattr(agg, "gar", None)
-    if type(gar) in (Krum,) + _LINEAR_RULES:
+    if type(gar) in (Krum,) + _LINEAR_RULES + _COORD_RULES:
         return True
     pc = getattr(agg, "analyze_pc", False)
     return isinstance(pc, str) and pc == "gram" and type(gar) is FedAvg
 
 
-def gram_resident_bytes(n: int, m: int) -> int:
+def _trim_ws_bytes(n: int, m: int, gar) -> int:
+    """The trim kernel's workspace, for a coordinate-wise rule only (0 for every other GAR)."""
+    return int(L.load().fc_trim_workspace_bytes(n, m)) if isinstance(gar, CoordinateTrim) else 0
+
+
+def gram_resident_bytes(n: int, m: int, gar=None) -> int:
     """Device bytes the "gram" route holds at once: m gradients and their packets, the batched
     encoder's, the Gram kernel's and the dot kernel's workspaces, the aggregate, a carried
-    vector (centered_clip) and the Gram matrix."""
+    vector (centered_clip) and the Gram matrix; for a coordinate-wise ``gar`` (trimmed_mean,
+    coordinate_median) the trim kernel's workspace too."""
     from .pipeline import packet_bytes
     lib = L.load()
     return (m * (4 * n + packet_bytes(n)) + int(lib.fc_workspace_bytes_batch(n, m))
             + int(lib.fc_gram_workspace_bytes(n, m)) + int(lib.fc_dot_workspace_bytes(n, m))
-            + 4 * n + 4 * n + 8 * m * m)
+            + 4 * n + 4 * n + 8 * m * m + _trim_ws_bytes(n, m, gar))
 
 
 def gram_route_k(agg, clients) -> int:
@@ -533,13 +546,16 @@ def gram_route_k(agg, clients) -> int:
     def no(why: str):
         raise NotImplementedError(f"the gram route (krum / pc_analysis='gram') needs {why}")
     cfg = getattr(agg, "aggregation_config", None) or {}
-    if type(agg.gar) not in (FedAvg, Krum) + _LINEAR_RULES:
-        no("the device FedAvg or Krum (or spectral_gram / geometric_median / centered_clip)")
+    if type(agg.gar) not in (FedAvg, Krum) + _LINEAR_RULES + _COORD_RULES:
+        no("the device FedAvg or Krum (or spectral_gram / geometric_median / centered_clip / "
+           "trimmed_mean / coordinate_median)")
     if agg.num_hierarchies != 0:
         no("no hierarchies (num_hierarchies == 0)")
     if cfg.get("devices", DEFAULT_DEVICES) not in (None, 1):
         no("one device")
     w = getattr(agg.gar, "gradient_weights", None)
+    if w is not None and isinstance(agg.gar, CoordinateTrim):
+        raise ValueError(f"{type(agg.gar).__name__} is unweighted: gradient_weights must be None")
     if w is not None and np.asarray(w).dtype != np.float32:
         no("float32 GAR weights")
     if len(clients) > L.FC_GRAM_MAX_M:
@@ -565,8 +581,8 @@ def gram_route_k(agg, clients) -> int:
     if not 0 < k < n:
         no(f"0 < k < n (k={k}, n={n})")
     b = cfg.get("device_budget_bytes")
-    if b and gram_resident_bytes(n, len(clients)) > int(b):
-        no(f"the round's packets to fit device_budget_bytes ({gram_resident_bytes(n, len(clients))}"
+    if b and gram_resident_bytes(n, len(clients), agg.gar) > int(b):
+        no(f"the round's packets to fit device_budget_bytes ({gram_resident_bytes(n, len(clients), agg.gar)}"
            f" > {int(b)} bytes)")
     return k
 
@@ -574,10 +590,12 @@ def gram_route_k(agg, clients) -> int:
 def gram_round(agg, clients, n: int, k: int, dev: torch.device) -> torch.Tensor:
     """One round on the "gram" route: upload, one batched 'top' encode, resolve, the packets'
     Gram matrix, then the FedAVG fold in row order (the "stream" route's bits), Krum's selected
-    row or a linear rule's fold.  Appends G's singular values to ``gar.Sigma_tracked`` for
+    row, a linear rule's fold or a coordinate-wise rule's kernel (which reads the packets alone:
+    the Gram matrix is then computed only for ``pc_analysis: "gram"``).  Appends G's singular
+    values to ``gar.Sigma_tracked`` for
     ``pc_analysis: "gram"`` (after the entry ``SpectralGram`` appends itself: two per round)."""
     m = len(clients)
-    need = gram_resident_bytes(n, m)
+    need = gram_resident_bytes(n, m, agg.gar)
     if need > _budget(agg, dev):
         raise NotImplementedError("the gram route (krum / pc_analysis='gram') needs the round's packets "
                                   f"to fit device_budget_bytes ({need} > {_budget(agg, dev)} bytes)")
@@ -593,14 +611,25 @@ def gram_round(agg, clients, n: int, k: int, dev: torch.device) -> torch.Tensor:
     for p in pk:
         p.release()
     del grads
-    gram = codec.gram(pk)
-    if isinstance(agg.gar, (Krum, LinearRule)):
-        out = agg.gar.aggregate_packets(pk, gram=gram)
+    return _gram_family(agg, agg.gar, pk)
+
+
+def _gram_family(agg, gar, pk) -> torch.Tensor:
+    """The "gram" route's consumers on a round's resident packets (also aggregate_wire's)."""
+    m = len(pk)
+    pc = getattr(agg, "analyze_pc", False) == "gram"
+    if isinstance(gar, CoordinateTrim):
+        out = gar.aggregate_packets(pk)
+        gram = codec.gram(pk) if pc else None
     else:
-        w = agg.gar._weights(m, np.float32)                         # gar.py:37-42 (persisted)
-        out = codec.decode_accumulate(pk, [float(x) for x in w])
-    if getattr(agg, "analyze_pc", False) == "gram":
-        agg.gar.Sigma_tracked.append(gram_singular_values(gram.cpu().numpy()))
+        gram = codec.gram(pk)
+        if isinstance(gar, (Krum, LinearRule)):
+            out = gar.aggregate_packets(pk, gram=gram)
+        else:
+            w = gar._weights(m, np.float32)                         # gar.py:37-42 (persisted)
+            out = codec.decode_accumulate(pk, [float(x) for x in w])
+    if pc:
+        gar.Sigma_tracked.append(gram_singular_values(gram.cpu().numpy()))
     return out
 
 
@@ -716,14 +745,15 @@ def wire_group(agg, n: int, m: int, dev: torch.device) -> int:
     return plan_group(n, m, _budget(agg, dev))
 
 
-def wire_resident_bytes(n: int, m: int, wire_total: int) -> int:
+def wire_resident_bytes(n: int, m: int, wire_total: int, gar=None) -> int:
     """Device bytes :func:`aggregate_wire` holds at once on the Gram family's path: the round's
     wire bytes and unpacked packets, the Gram and dot workspaces, the aggregate, a carried vector
-    and the Gram matrix."""
+    and the Gram matrix; for a coordinate-wise ``gar`` the trim kernel's workspace too."""
     from .pipeline import packet_bytes
     lib = L.load()
     return (wire_total + m * packet_bytes(n) + int(lib.fc_gram_workspace_bytes(n, m))
-            + int(lib.fc_dot_workspace_bytes(n, m)) + 4 * n + 4 * n + 8 * m * m)
+            + int(lib.fc_dot_workspace_bytes(n, m)) + 4 * n + 4 * n + 8 * m * m
+            + _trim_ws_bytes(n, m, gar))
 
 
 def _wire_no(why: str):
@@ -768,7 +798,8 @@ def aggregate_wire(self, payloads, n: Optional[int] = None) -> None:
       written, the groups are :func:`wire_fold_groups` of the payload sizes, the bits are the
       same and ``agg_path = "wire-fold"``.  The key leaves the Gram family below untouched:
       those consumers read slotted packets, so they still unpack and answer ``"wire"``.
-    * ``krum``, ``spectral_gram`` / ``geometric_median`` / ``centered_clip`` and
+    * ``krum``, ``spectral_gram`` / ``geometric_median`` / ``centered_clip``, ``trimmed_mean`` /
+      ``coordinate_median`` and
       ``pc_analysis: "gram"``: at most ``FC_GRAM_MAX_M`` payloads, all resident within the budget;
       ``codec.gram`` then ``gar.aggregate_packets`` exactly as the "gram" route does.
     Hierarchies, payloads of differing n and a round that does not fit raise
@@ -785,11 +816,14 @@ def aggregate_wire(self, payloads, n: Optional[int] = None) -> None:
     gar = self.gar
     family = gram_wanted(self)
     if not family and type(gar) is not FedAvg:
-        no("the device FedAvg, Krum, spectral_gram, geometric_median or centered_clip")
+        no("the device FedAvg, Krum, spectral_gram, geometric_median, centered_clip, trimmed_mean "
+           "or coordinate_median")
     cfg = getattr(self, "aggregation_config", None) or {}
     if cfg.get("devices", DEFAULT_DEVICES) not in (None, 1):
         no("one device")
     w = getattr(gar, "gradient_weights", None)
+    if w is not None and isinstance(gar, CoordinateTrim):
+        raise ValueError(f"{type(gar).__name__} is unweighted: gradient_weights must be None")
     if w is not None and np.asarray(w).dtype != np.float32:
         no("float32 GAR weights")
     if family and m > L.FC_GRAM_MAX_M:
@@ -810,8 +844,8 @@ def aggregate_wire(self, payloads, n: Optional[int] = None) -> None:
         total += (a.size + 255) & ~255
     n = int(n)
     b = cfg.get("device_budget_bytes")
-    if family and b and wire_resident_bytes(n, m, total) > int(b):
-        no(f"the round's packets to fit device_budget_bytes ({wire_resident_bytes(n, m, total)}"
+    if family and b and wire_resident_bytes(n, m, total, gar) > int(b):
+        no(f"the round's packets to fit device_budget_bytes ({wire_resident_bytes(n, m, total, gar)}"
            f" > {int(b)} bytes)")
     # ---- the device's part ----
     dev = _device_of(self)
@@ -838,20 +872,13 @@ def aggregate_wire(self, payloads, n: Optional[int] = None) -> None:
                 for (a, h), o in zip(part, offs)]
 
     if family:
-        need = wire_resident_bytes(n, m, total)
+        need = wire_resident_bytes(n, m, total, gar)
         if need > _budget(self, dev):
             no(f"the round's packets to fit device_budget_bytes ({need} > {_budget(self, dev)} bytes)")
         wires = upload(hosts)
         pk = codec.unpack(wires, packets_for(m))
         del wires
-        gram = codec.gram(pk)
-        if isinstance(gar, (Krum, LinearRule)):
-            out = gar.aggregate_packets(pk, gram=gram)
-        else:
-            wts = gar._weights(m, np.float32)                       # gar.py:37-42 (persisted)
-            out = codec.decode_accumulate(pk, [float(x) for x in wts])
-        if getattr(self, "analyze_pc", False) == "gram":
-            gar.Sigma_tracked.append(gram_singular_values(gram.cpu().numpy()))
+        out = _gram_family(self, gar, pk)
     elif cfg.get("wire_fold", False):
         wts = gar._weights(m, np.float32)                           # gar.py:37-42 (persisted)
         groups = wire_fold_groups([a.size for a, _ in hosts], n, _budget(self, dev))
@@ -912,6 +939,10 @@ class Aggregator:
             return GeometricMedian(aggregation_config=self.aggregation_config)
         if scheme == "centered_clip":
             return CenteredClip(aggregation_config=self.aggregation_config)
+        if scheme == "trimmed_mean":
+            return TrimmedMean(aggregation_config=self.aggregation_config)
+        if scheme == "coordinate_median":
+            return CoordinateMedian(aggregation_config=self.aggregation_config)
         if scheme == "fed_spectral_avg":
             raise NotImplementedError("SpectralFedAvg is outside the codec hot path (DESIGN.md §8)")
         raise NotImplementedError

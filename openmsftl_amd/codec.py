@@ -8,6 +8,7 @@
     agg = decode_accumulate(pkts, w)       # aggregation.py:61-63 + gar.py:44, bit-exact fp32
     gm  = gram(pkts)                       # G @ G.T in float64 straight from the packets
     b   = dot_dense(pkts, v)               # [G @ v, v @ v] in float64 (v=None: row sums, n)
+    tm  = trimmed_mean(pkts, b)            # coordinate-wise trimmed mean / median, bit-exact fp32
     w   = pack(pkt); raw = w.tobytes()     # the compact wire form: the kept entries alone
     pkt = unpack(wire_from_host(raw))      # validated host bytes back into a slotted packet
     agg = fold_wire(wires, w)              # decode_accumulate(unpack(wires), w) without the unpack
@@ -925,6 +926,71 @@ def dot_dense(packets: Sequence[Packet], v: Optional[torch.Tensor] = None,
     views = views_tensor(packets, [1.0] * m, dev)
     L.check(lib.fc_packets_dot(_vp(views), m, n, _vp(v), _vp(out), _vp(ws.buf), ws.nbytes,
                                _stream(dev)), "fc_packets_dot")
+    return out
+
+
+class TrimWorkspace:
+    """Per-(device, stream) scratch of :func:`trimmed_mean`, taken only when
+    ``fc_trim_workspace_bytes`` is not 0 (needs no zeroing)."""
+
+    _cache: dict = {}
+
+    def __init__(self, nbytes: int, device: torch.device):
+        self.nbytes = nbytes
+        self.buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+    @classmethod
+    def get(cls, n: int, m: int, device: torch.device) -> Optional["TrimWorkspace"]:
+        need = int(L.load().fc_trim_workspace_bytes(n, m))
+        if need == 0:
+            return None
+        key = (device.index if device.index is not None else torch.cuda.current_device(),
+               torch.cuda.current_stream(device).cuda_stream)
+        ws = cls._cache.get(key)
+        if ws is None or ws.nbytes < need:
+            ws = cls(need, device)
+            cls._cache[key] = ws
+        return ws
+
+
+def _check_trim(m: int, trim) -> int:
+    """The (m, trim) pairs :func:`trimmed_mean` takes: the checked trim as an int."""
+    if m > L.FC_GRAM_MAX_M:
+        raise ValueError(f"trimmed_mean takes at most {L.FC_GRAM_MAX_M} packets (got {m})")
+    if isinstance(trim, bool) or not isinstance(trim, (int, np.integer)):
+        raise ValueError(f"trim must be an integer (got {trim!r})")
+    trim = int(trim)
+    if trim < 0:
+        raise ValueError(f"trim must not be negative (got {trim})")
+    if 2 * trim >= m:
+        raise ValueError(f"trim={trim} leaves nothing of {m} packets (2 * trim must be < m)")
+    return trim
+
+
+def trimmed_mean(packets: Sequence[Packet], trim: int,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The (n,) float32 coordinate-wise trimmed mean of the rows :func:`decode` would make of the
+    packets (the rows :func:`gram` uses), computed straight from them (fc_packets_trim): per
+    coordinate the m values in ``np.sort``'s order, the ``trim`` smallest and largest dropped,
+    the rest added in ascending order in float32 from +0.0 and divided by ``float32(m - 2 trim)``.
+    ``trim = (m - 1) // 2`` is the coordinate-wise median.  At most ``FC_GRAM_MAX_M`` idx/val
+    packets of one length; ``0 <= trim`` and ``2 * trim < m``."""
+    if not packets:
+        raise ValueError("no packets")
+    m, n, dev = len(packets), packets[0].n, packets[0].val.device
+    trim = _check_trim(m, trim)
+    _check_idxval_packets(packets)
+    lib = L.load()
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=dev)
+    if (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != dev
+            or tuple(out.shape) != (n,) or not out.is_contiguous() or out.data_ptr() % 16):
+        raise ValueError("out must be a contiguous 16-byte aligned (n,) float32 tensor on the "
+                         "packets' device")
+    ws = TrimWorkspace.get(n, m, dev)
+    views = views_tensor(packets, [1.0] * m, dev)
+    L.check(lib.fc_packets_trim(_vp(views), m, n, trim, _vp(out), _vp(ws.buf if ws else None),
+                                ws.nbytes if ws else 0, _stream(dev)), "fc_packets_trim")
     return out
 
 

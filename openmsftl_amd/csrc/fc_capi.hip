@@ -1248,3 +1248,49 @@ int fc_packets_dot(const fc_packet_view* views_dev, int m, uint64_t n, const flo
 }
 
 }  // extern "C"
+
+// ---- coordinate-wise trimmed mean of a round's packets (fc_trim.hip) --------------------------
+// One workgroup per chunk; the window and the tile's LDS come from m alone.  No workspace.
+namespace {
+int trim_lds_setup() {
+  static int rc = [] {
+    return hipFuncSetAttribute((const void*)k_trim, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)(kTTile * sizeof(float))) == hipSuccess ? 0 : -1;
+  }();
+  return rc;
+}
+}  // namespace
+
+extern "C" {
+
+size_t fc_trim_workspace_bytes(uint64_t n, int m) {
+  (void)n; (void)m;
+  return 0;
+}
+
+int fc_packets_trim(const fc_packet_view* views_dev, int m, uint64_t n, int trim, float* out,
+                    void* ws, size_t ws_bytes, fc_stream_t stream) {
+  FC_CHECK(views_dev != nullptr, "views_dev is NULL");
+  FC_CHECK(out != nullptr, "out is NULL");
+  FC_CHECK(m >= 1 && m <= FC_GRAM_MAX_M, "m=%d outside [1, %d]", m, FC_GRAM_MAX_M);
+  FC_CHECK(trim >= 0 && 2 * (int64_t)trim < (int64_t)m, "trim=%d outside [0, m/2) for m=%d", trim, m);
+  FC_CHECK(n >= 1 && n <= 0xffffffffull, "n=%llu outside [1, 2^32-1]", (unsigned long long)n);
+  FC_CHECK(((uintptr_t)out & 15) == 0, "out must be 16-byte aligned");
+  FC_CHECK(((uintptr_t)ws & 15) == 0, "workspace must be 16-byte aligned");
+  const size_t need = fc_trim_workspace_bytes(n, m);
+  FC_CHECK(ws != nullptr || need == 0, "workspace is NULL");
+  if (ws_bytes < need)
+    return fail(FC_ERR_WORKSPACE, "workspace %zu B < %zu B needed", ws_bytes, need);
+  if (trim_lds_setup() != 0)
+    return fail(FC_ERR_HIP, "k_trim: cannot reserve %zu B of LDS", kTTile * sizeof(float));
+  TrimArgs a;
+  memset(&a, 0, sizeof a);
+  a.views = views_dev; a.out = out; a.n = n; a.m = (uint32_t)m; a.trim = (uint32_t)trim;
+  a.div = (float)(m - 2 * trim);
+  const size_t lds = (size_t)m * trim_window((uint32_t)m) * sizeof(float);
+  hipLaunchKernelGGL(k_trim, dim3(num_chunks(n)), dim3(kTBlock), lds, (hipStream_t)stream, a);
+  FC_LAUNCHED("k_trim");
+  return FC_OK;
+}
+
+}  // extern "C"

@@ -28,6 +28,13 @@ float32 fold (``codec.decode_accumulate``).  ``SpectralGram`` is the analytic br
 reference's ``SpectralFedAvg`` (gar.py:123-134, ``fast_lr_decomposition``) restated on the
 Gram, ``GeometricMedian`` the smoothed Weiszfeld iteration (RFA), ``CenteredClip`` centered
 clipping (Karimireddy, He, Jaggi, ICML 2021).
+
+``CoordinateTrim`` is the base of the coordinate-wise rules (Yin, Chen, Ramchandran, Bartlett,
+ICML 2018), which are not linear in the rows: ``TrimmedMean`` drops the ``b`` smallest and
+largest of every coordinate's M values and takes the float32 mean of the rest,
+``CoordinateMedian`` is ``b = (M - 1) // 2``.  ``aggregate_packets`` is one kernel over the
+packets (``codec.trimmed_mean``): only a column's non-zeros are ordered, no Gram matrix is
+needed, no client is excluded as a whole and the rules take no weights.
 """
 from __future__ import annotations
 
@@ -410,3 +417,76 @@ class CenteredClip(LinearRule):
 
     def _after(self, agg: torch.Tensor) -> None:
         self.v = agg.clone()
+
+
+# ---- coordinate-wise rules: the trimmed mean and the median of every coordinate --------------
+class CoordinateTrim(GAR):
+    """A coordinate-wise rule (Yin, Chen, Ramchandran, Bartlett, ICML 2018): per coordinate the M
+    clients' values are ordered as ``np.sort`` does, the ``trim`` smallest and largest dropped and
+    the float32 mean of the rest taken (``codec.trimmed_mean``: ascending float32 sum from +0.0,
+    then one division).  ``aggregate_packets`` reads the packets alone: no dense G and no Gram
+    matrix.  ``trim`` holds the count used in the last round.
+
+    The rules are unweighted and exclude no client as a whole: a ``gradient_weights`` that is not
+    None raises (a DGA weight vector silently ignored would be a wrong result), and a client with
+    a NaN takes part with its other coordinates."""
+
+    def __init__(self, aggregation_config):
+        GAR.__init__(self, aggregation_config=aggregation_config)
+        self.trim = None
+
+    def _trim_of(self, m: int) -> int:
+        """The count b for a round of m clients."""
+        raise NotImplementedError
+
+    def aggregate(self, G, client_ids=None):
+        raise NotImplementedError(f"{type(self).__name__} reads the clients' geometry from their "
+                                  "packets (aggregate_packets, the Aggregator's gram route); a "
+                                  "dense G is not taken")
+
+    def aggregate_packets(self, packets: Sequence["codec.Packet"], out=None) -> torch.Tensor:
+        if self.gradient_weights is not None:
+            raise ValueError(f"{type(self).__name__} is unweighted: gradient_weights must be None")
+        self.trim = self._trim_of(len(packets))
+        return codec.trimmed_mean(packets, self.trim, out=out)
+
+
+class TrimmedMean(CoordinateTrim):
+    """The coordinate-wise trimmed mean.  Config keys: ``trim_frac`` (default 0.1) gives
+    ``b = int(trim_frac * M)``, or an integer ``trim_count`` gives b itself; both, a negative
+    value or ``2 b >= M`` raise ``ValueError``."""
+
+    def __init__(self, aggregation_config):
+        CoordinateTrim.__init__(self, aggregation_config=aggregation_config)
+        frac = aggregation_config.get("trim_frac", None)
+        count = aggregation_config.get("trim_count", None)
+        if frac is not None and count is not None:
+            raise ValueError("give trim_frac or trim_count, not both")
+        if count is not None:
+            if isinstance(count, bool) or not isinstance(count, (int, np.integer)):
+                raise ValueError(f"trim_count must be an integer (got {count!r})")
+            if count < 0:
+                raise ValueError(f"trim_count must not be negative (got {count})")
+        else:
+            frac = 0.1 if frac is None else frac
+            if isinstance(frac, bool) or not isinstance(frac, (int, float, np.floating, np.integer)) \
+                    or not frac >= 0:
+                raise ValueError(f"trim_frac must be a number >= 0 (got {frac!r})")
+        self.trim_frac = None if count is not None else float(frac)
+        self.trim_count = None if count is None else int(count)
+
+    def _trim_of(self, m: int) -> int:
+        key = "trim_frac" if self.trim_count is None else "trim_count"
+        b = int(self.trim_frac * m) if self.trim_count is None else self.trim_count
+        if 2 * b >= m:
+            raise ValueError(f"{key}={getattr(self, key)} trims {b} values at each end of {m} clients: "
+                             "nothing is left (2 b must be < M)")
+        return b
+
+
+class CoordinateMedian(CoordinateTrim):
+    """The coordinate-wise median: ``b = (M - 1) // 2``, the middle value for odd M and the
+    float32 mean of the two middle values for even M."""
+
+    def _trim_of(self, m: int) -> int:
+        return (m - 1) // 2
