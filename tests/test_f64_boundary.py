@@ -181,6 +181,7 @@ def test_gpu_top_f64_sizes_and_ties(n, f):
 @pytest.mark.gpu
 def test_gpu_philox_rand_f64_selects_the_fp32_set():
     """Native rand-k keys depend on the index only: the float64 path keeps the same set."""
+    # (against oracle.philox itself: tests/test_f64_gpu.py::test_rand_philox_f64_matches_oracle)
     n, f = 100_003, 0.1
     g = np.random.default_rng(1).standard_normal(n) + 3.0          # no zeros
     cfg = {"compression_function": "rand", "fraction_coordinate": f, "rng": "philox", "seed": 77}
@@ -305,6 +306,7 @@ def _f64_inputs(kind, n, seed):
 def test_gpu_sampled_top_f64_equals_exact(kind, n, f):
     """Sampled bracket + one streaming pass + exact candidate select gives the exact radix
     select's bytes; on Gaussian-like gradients without a retry."""
+    # (against the NumPy oracle, branch by branch: tests/test_f64_gpu.py)
     import torch
     from openmsftl_amd import codec
     g = torch.from_numpy(_f64_inputs(kind, n, n % 1000)).cuda()
