@@ -71,6 +71,7 @@ typedef void* fc_stream_t; /* hipStream_t */
 #define FC_CODEC_DROPOUT_BIASED 3
 #define FC_CODEC_DROPOUT_UNBIASED 4
 #define FC_CODEC_QSGD 5      /* opt-in: the reference raises NotImplementedError (:62-64)    */
+#define FC_CODEC_SIGN 6      /* opt-in, no reference counterpart: scaled sign (fc_sign_encode) */
 
 /* key sources for fc_topk_encode */
 #define FC_KEY_MAGNITUDE 0   /* |g| (top-k) */
@@ -82,6 +83,7 @@ typedef void* fc_stream_t; /* hipStream_t */
 #define FC_FMT_QSGD 2        /* packed W-bit codes (sign | level), fc_qsgd_code_words */
 #define FC_FMT_DENSE 3       /* header of fc_topk_encode_dense: the dense q is the product;
                                 idx/val/cnt/qoff are scratch (not a decodable packet) */
+#define FC_FMT_SIGN 4        /* uint32 word[fc_sign_words(n)] of sign bits + the scale in hdr.p */
 
 /* Slotted packet layout: the gradient is cut into chunks of FC_CHUNK elements; chunk c's
  * entries (ascending index order) live at [c*FC_CHUNK, c*FC_CHUNK + cnt[c]) of idx/val (and
@@ -121,7 +123,7 @@ typedef struct fc_packet_hdr {
 typedef struct fc_packet_view {
   const void* idx;              /* FC_FMT_IDXVAL: uint16 chunk-local indices; FC_FMT_QSGD: uint32 codes */
   const float* val;
-  const uint32_t* bitmap;       /* FC_FMT_BITMAP                        */
+  const uint32_t* bitmap;       /* FC_FMT_BITMAP; FC_FMT_SIGN: the words */
   const uint32_t* cnt;          /* ceil(N/FC_CHUNK) entries per chunk   */
   const fc_packet_hdr* hdr;
   const uint64_t* qoff;         /* FC_FMT_IDXVAL: quarter offsets per chunk (see above) */
@@ -516,6 +518,71 @@ int fc_qsgd_decode(const fc_packet_view* pkt, uint64_t n, float* out, fc_stream_
  * into the partial sum already in out. */
 int fc_qsgd_decode_accumulate(const fc_packet_view* views_dev, int m, uint64_t n, float* out,
                               int continue_sum, fc_stream_t stream);
+
+/* ---- scaled sign with error feedback, its FedAVG fold and the majority vote (fc_sign.hip) ----
+ * The 1-bit codec (EF-signSGD: Karimireddy, Rebjock, Stich, Jaggi, ICML 2019; opt-in, no reference
+ * counterpart) and the cheapest coordinate-wise robust rule over its packets (signSGD with
+ * majority vote: Bernstein, Zhao, Azizzadenesheli, Anandkumar, ICLR 2019).  For a float32
+ * gradient g[n], n >= 1, and an optional float32 residual e[n]:
+ *   a[t] = fl32(g[t] + e[t]), one IEEE add (so -0.0 + +0.0 = +0.0); a[t] = g[t] without a residual
+ *   s    = fl32(S / (double)n), S = sum_t (double)|a[t]| in float64, in an order fixed by n alone
+ *          (no floating-point atomics: two calls give the same bits); non-finite elements make s
+ *          inf or NaN by plain IEEE arithmetic, nothing is special-cased
+ *   b[t] = the IEEE sign bit of a[t] (-0.0 is negative, a NaN goes by its sign bit; the sign of a
+ *          NaN that the add itself produces, inf + -inf, is the hardware's), little-endian: bit
+ *          t % 32 of uint32 word[t / 32], the convention of mask_bits.  fc_sign_words(n) words:
+ *          ceil(n / 32) rounded up to a multiple of 4; bits at and past n and the pad words are
+ *          written as zero
+ *   q[t] = b[t] ? -s : +s                       (fc_sign_decode)
+ *   e'[t] = fl32(a[t] - q[t]), one IEEE subtract (res_out; a non-finite gradient poisons it exactly
+ *          as this arithmetic says)
+ *   header: codec FC_CODEC_SIGN, format FC_FMT_SIGN, n, k = n_entries = n, status FC_STATUS_OK,
+ *          p = (double)s, every other field zero.  A view carries the words in `bitmap`; idx, val,
+ *          cnt and qoff are NULL.
+ * fc_sign_encode: g, res_in (NULL: none), res_out (NULL: not wanted), words all 16-B aligned;
+ *   res_out may not overlap g or res_in (the rule of fc_topk_encode_ef); n_words >=
+ *   fc_sign_words(n).  Two launches (the norm pass, whose last arriver writes the header, and the
+ *   streaming pass), neither waits in-kernel for another workgroup: no fc_fused_order_* handling.
+ *   ws: fc_sign_workspace_bytes(n) bytes, 8-B aligned, zeroed once (self-cleaning afterwards), one
+ *   per stream.  Bytes: 8N (16N with a residual) read, N/8 (+ 4N) written.
+ * fc_sign_decode: pkt a HOST pointer to one view; out float32[n], 16-B aligned.
+ * fc_sign_fold: the FedAVG of m packets (views_dev: DEVICE array of m views, the weights in the
+ *   views, 1 <= m <= 65535) with the bits of fc_weighted_sum_dense on the m decoded rows: per
+ *   coordinate the terms +-c_i, c_i = fl32(w_i * s_i), added in row order from +0.0
+ *   (continue_sum != 0: from the sum already in out, as fc_decode_accumulate_continue; a round
+ *   cut into groups gives the bits of one call).  Bytes: m N/8 + 4N (+ 4N when continuing).
+ * fc_sign_vote: neg = #{i : b_i[t]}; out[t] = -eta if 2 neg > m, +eta if 2 neg < m, +0.0 on a tie.
+ *   Integer counting: any client order gives the same result; weights and scales play no part.
+ * Both: one launch, no workgroup waits for another, no atomics, stream-ordered, no allocation, no
+ *   workspace; out float32[n], 16-B aligned; every view's words 16-B aligned (the caller's
+ *   contract: the table is device memory).
+ * fc_sign_wire_validate: HOST bytes, no GPU (openmsftl_amd/csrc/fc_sign_host.h).  The wire form is
+ *   a 128-byte header (uint32 magic "FCS1", uint32 version 1, uint64 total_bytes, 16 zero bytes,
+ *   the canonical fc_packet_hdr above) and 4 fc_sign_words(n) bytes of words: a function of n
+ *   alone.  FC_OK, or FC_ERR_ARG with the reason in fc_last_error(), reading nothing past len:
+ *   a wrong length, magic or version; n = 0 or n != n_expected (unless that is 0); codec or format
+ *   other than sign; k or n_entries != n; a status other than OK; a field that must be zero; a
+ *   negative p (NaN excepted); a p that is not exactly a float32 value; a set bit at or past n; a
+ *   non-zero pad word.  fc_wire_validate rejects these bytes by their magic.
+ * fc_sign_fold_form (measurement, not thread-safe): how the following fc_sign_fold / fc_sign_vote
+ *   launches bring the words to the waves: 0 scalar loads and 1 vector loads with v_readlane
+ *   (the 64-bit word wave-uniform, used as a lane mask), 2 one word per lane (the default: the
+ *   fastest measured), -1 the default.  The results do not depend on it.
+ * Argument errors (NULL, n, m, alignment, overlap, n_words: FC_ERR_ARG; a short workspace:
+ *   FC_ERR_WORKSPACE) are reported before the GPU is touched. */
+uint64_t fc_sign_words(uint64_t n);
+size_t fc_sign_workspace_bytes(uint64_t n);
+int fc_sign_encode(const float* g, const float* res_in /* NULL: none */,
+                   float* res_out /* NULL: not wanted */, uint64_t n, uint32_t* words,
+                   uint64_t n_words, fc_packet_hdr* hdr, void* ws, size_t ws_bytes,
+                   fc_stream_t stream);
+int fc_sign_decode(const fc_packet_view* pkt, uint64_t n, float* out, fc_stream_t stream);
+int fc_sign_fold(const fc_packet_view* views_dev, int m, uint64_t n, float* out, int continue_sum,
+                 fc_stream_t stream);
+int fc_sign_vote(const fc_packet_view* views_dev, int m, uint64_t n, float eta, float* out,
+                 fc_stream_t stream);
+int fc_sign_wire_validate(const void* host_bytes, size_t len, uint64_t n_expected /* 0 = any */);
+int fc_sign_fold_form(int form);
 
 /* ---- float64 gradients ------------------------------------------------------------
  * The reference reaches the codec with float64 gradients after RandomGaussian with

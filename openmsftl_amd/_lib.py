@@ -17,8 +17,10 @@ FC_OK = 0
 FC_STATUS_OK, FC_STATUS_RETRY_EXACT, FC_STATUS_OVERFLOW, FC_STATUS_TIMEOUT = 0, 1, 2, 3
 FC_CODEC_TOP, FC_CODEC_RAND, FC_CODEC_DROPOUT_BIASED, FC_CODEC_DROPOUT_UNBIASED = 1, 2, 3, 4
 FC_CODEC_QSGD = 5
+FC_CODEC_SIGN = 6
 FC_KEY_MAGNITUDE, FC_KEY_PHILOX = 0, 1
 FC_FMT_IDXVAL, FC_FMT_BITMAP, FC_FMT_QSGD, FC_FMT_DENSE = 0, 1, 2, 3
+FC_FMT_SIGN = 4
 FC_PART_SAMPLE, FC_PART_FINISH = 1, 2
 FC_CHUNK = 8192
 FC_GRAM_MAX_M = 128
@@ -83,7 +85,15 @@ class WireHdr(ctypes.Structure):
                 ("nch", ctypes.c_uint32), ("status", ctypes.c_uint32), ("pkt", PacketHdr)]
 
 
+class SignWireHdr(ctypes.Structure):
+    """fc_sign_wire_hdr: the first 128 bytes of a sign packet's wire form."""
+    _fields_ = [("magic", ctypes.c_uint32), ("version", ctypes.c_uint32),
+                ("total_bytes", ctypes.c_uint64), ("zero", ctypes.c_uint32 * 4), ("pkt", PacketHdr)]
+
+
+SIGN_MAGIC = 0x31534346            # "FCS1"
 WIRE_HDR_BYTES = 128
+assert ctypes.sizeof(SignWireHdr) == WIRE_HDR_BYTES
 assert ctypes.sizeof(WireJob) == 16
 assert ctypes.sizeof(WireHdr) == WIRE_HDR_BYTES
 assert ctypes.sizeof(PermState) == 2520
@@ -145,6 +155,14 @@ SIGNATURES = {
     "fc_qsgd_encode": (_i32, [_vp, _u64, _i32, _u64, _u64, _vp, _u64, _vp, _vp, _sz, _vp]),
     "fc_qsgd_decode": (_i32, [ctypes.POINTER(PacketView), _u64, _vp, _vp]),
     "fc_qsgd_decode_accumulate": (_i32, [_vp, _i32, _u64, _vp, _i32, _vp]),
+    "fc_sign_words": (_u64, [_u64]),
+    "fc_sign_workspace_bytes": (_sz, [_u64]),
+    "fc_sign_encode": (_i32, [_vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _sz, _vp]),
+    "fc_sign_decode": (_i32, [ctypes.POINTER(PacketView), _u64, _vp, _vp]),
+    "fc_sign_fold": (_i32, [_vp, _i32, _u64, _vp, _i32, _vp]),
+    "fc_sign_vote": (_i32, [_vp, _i32, _u64, ctypes.c_float, _vp, _vp]),
+    "fc_sign_wire_validate": (_i32, [_vp, _sz, _u64]),
+    "fc_sign_fold_form": (_i32, [_i32]),
     "fc_topk_dense_f64": (_i32, [_vp, _u64, _u64, _i32, _u64, _u64, _vp, _vp, _sz, _vp]),
     "fc_topk_dense_f64_sampled": (_i32, [_vp, _u64, _u64, _vp, _vp, _sz, _vp, _vp]),
     "fc_mask_dense_f64": (_i32, [_vp, _u64, _i32, _vp, _dbl, _u64, _u64, _vp, _vp]),

@@ -82,7 +82,7 @@ from . import _lib as L
 from . import codec
 from .compression import Compression, bitmask_words, kept_count
 from .gar import (CenteredClip, CoordinateMedian, CoordinateTrim, FedAvg, GeometricMedian, Krum,
-                  LinearRule, SpectralGram, TrimmedMean, gram_singular_values)
+                  LinearRule, SignMajority, SpectralGram, TrimmedMean, gram_singular_values)
 from .pipeline import HostFedAvg, MtRedraw, RowCodec, RowPlan
 
 
@@ -633,6 +633,155 @@ def _gram_family(agg, gar, pk) -> torch.Tensor:
     return out
 
 
+# ---- the "sign" route: a round of scaled-sign clients, only their N/8-byte packets resident ----
+def _sign_no(why: str):
+    raise NotImplementedError(f"the sign route (sign packets: fed_avg / sign_majority) needs {why}")
+
+
+def sign_packet_bytes(n: int) -> int:
+    """Device bytes of one resident sign packet: its words and header, rounded up to 256."""
+    return (4 * int(L.load().fc_sign_words(n)) + L.HDR_BYTES + 255) & ~255
+
+
+def sign_route(agg, clients) -> bool:
+    """Does this round take the "sign" route?  True when every client is the drop-in
+    ``Compression`` with 'sign', the gradients are 1-D float32 of one length n > 0, there are no
+    hierarchies, one device is used and the GAR is the device ``FedAvg`` with float32 or no
+    weights (and ``"sign_packets"`` is not False), or ``SignMajority``.  A ``fed_avg`` round
+    outside these conditions answers False (the generic routes take it); a ``sign_majority`` round
+    outside them raises ``NotImplementedError`` naming the condition, and so does a round of 'sign'
+    clients under a scheme that has no consumer of sign packets (Krum, the linear rules, the trim
+    rules, ``pc_analysis: "gram"``).  Touches no GPU (the budget is checked here only when
+    ``device_budget_bytes`` is configured; :func:`sign_round` checks the default budget)."""
+    gar = getattr(agg, "gar", None)
+    cfg = getattr(agg, "aggregation_config", None) or {}
+    major = type(gar) is SignMajority
+    all_sign = all(getattr(c.C, "compression_function", None) == "sign" for c in clients)
+    if not all_sign:
+        if major:
+            _sign_no("every client to compress with 'sign'")
+        return False
+    if gram_wanted(agg):
+        what = type(gar).__name__ if type(gar) is not FedAvg else "pc_analysis 'gram'"
+        raise NotImplementedError(f"{what} has no consumer of sign packets: a round of 'sign' "
+                                  "clients takes fed_avg or sign_majority")
+    if not major and (type(gar) is not FedAvg or cfg.get("sign_packets", True) is False):
+        return False
+
+    def no(why: str):
+        if major:
+            _sign_no(why)
+        return False
+
+    if major and gar.gradient_weights is not None:
+        raise ValueError("SignMajority is unweighted: gradient_weights must be None")
+    if not all(isinstance(c.C, Compression) for c in clients):
+        return no("every client to be the drop-in Compression")
+    if agg.num_hierarchies != 0:
+        return no("no hierarchies (num_hierarchies == 0)")
+    if cfg.get("devices", DEFAULT_DEVICES) not in (None, 1):
+        return no("one device")
+    w = getattr(gar, "gradient_weights", None)
+    if w is not None and np.asarray(w).dtype != np.float32:
+        return no("float32 GAR weights")
+    n = None
+    for c in clients:
+        g = np.asarray(c.grad)
+        if g.ndim != 1 or g.dtype != np.float32:
+            return no("1-D float32 gradients")
+        if n is not None and g.shape[0] != n:
+            return no("gradients of one length")
+        n = g.shape[0]
+    if n == 0:
+        return no("a gradient length n > 0")
+    b = cfg.get("device_budget_bytes")
+    if major and b and len(clients) * sign_packet_bytes(n) + 8 * n > int(b):
+        _sign_no(f"the round's packets to fit device_budget_bytes "
+                 f"({len(clients) * sign_packet_bytes(n) + 8 * n} > {int(b)} bytes): the majority "
+                 "vote reads every packet at once")
+    return True
+
+
+def sign_round(agg, clients, n: int, dev: torch.device) -> torch.Tensor:
+    """One round on the "sign" route.  The clients are uploaded and encoded one at a time
+    (``codec.encode_sign``; with error feedback each client's residual advances exactly once,
+    committed after its encode was issued), so only their N/8-byte packets stay resident.
+    ``FedAvg`` folds them in row order in groups sized by the budget, continuing the sum
+    (``codec.fold_sign``: the "dense-fold" route's bits); ``SignMajority`` votes over all of them
+    and raises ``NotImplementedError`` naming the budget when they do not fit."""
+    gar, m = agg.gar, len(clients)
+    major = type(gar) is SignMajority
+    per, budget = sign_packet_bytes(n), _budget(agg, dev)
+    room = budget - 8 * n                      # beside the aggregate and the gradient in flight
+    if major and m * per > room:
+        _sign_no(f"the round's packets to fit device_budget_bytes ({m * per + 8 * n} > {budget} "
+                 "bytes): the majority vote reads every packet at once")
+    group = m if major else int(max(1, min(m, 65535, room // per)))
+    for c in clients:                          # every residual checked before one advances
+        if c.C.error_feedback:
+            c.C._ef_buffers(n, dev, allocate=False)
+    w = None if major else gar._weights(m, np.float32)                # gar.py:37-42 (persisted)
+    cache = agg.__dict__.setdefault("_sign_packets", {})
+    slots = cache.get((n, dev))
+    if slots is None or len(slots) < group:
+        cache.clear()
+        slots = cache[(n, dev)] = [codec.SignPacket.alloc(n, dev) for _ in range(group)]
+    out = torch.empty(n, dtype=torch.float32, device=dev)
+    agg.sign_groups = 0
+    for s in range(0, m, group):
+        part = clients[s:s + group]
+        for c, slot in zip(part, slots):
+            g = torch.from_numpy(np.ascontiguousarray(c.grad)).to(dev)
+            if c.C.error_feedback:
+                res, spare = c.C._ef_buffers(n, dev)
+                _, new = codec.encode_sign(g, res, residual_out=spare, packet=slot)
+                c.C._ef_commit(res, new, True)
+            else:
+                codec.encode_sign(g, packet=slot)
+        pk = slots[:len(part)]
+        if major:
+            gar.aggregate_packets(pk, out=out)
+        else:
+            codec.fold_sign(pk, [float(x) for x in w[s:s + len(part)]], out=out, continue_sum=s > 0)
+        agg.sign_groups += 1
+    return out
+
+
+def sign_wire_round(agg, hosts, n: int, dev: torch.device) -> torch.Tensor:
+    """aggregate_wire's round of validated sign payloads (``hosts``: what ``codec._sign_check``
+    returned for each): uploaded into one cached device slab and folded in groups
+    (:func:`wire_fold_groups`, ``fed_avg``) or voted over, all resident (``sign_majority``)."""
+    gar, m = agg.gar, len(hosts)
+    sizes = [a.size for a, _ in hosts]
+    budget = _budget(agg, dev)
+    if type(gar) is SignMajority:
+        total = sum((b + 255) & ~255 for b in sizes)
+        if total + 4 * n > budget:
+            _wire_no(f"the round's sign packets to fit device_budget_bytes ({total + 4 * n} > "
+                     f"{budget} bytes): the majority vote reads every packet at once")
+        groups = [range(0, m)]
+        wts = None
+    else:
+        groups = wire_fold_groups(sizes, n, budget)
+        wts = gar._weights(m, np.float32)                               # gar.py:37-42 (persisted)
+    cache = agg.__dict__.setdefault("_sign_wire", {})
+    out = torch.empty(n, dtype=torch.float32, device=dev)
+    for gi, g in enumerate(groups):
+        part = hosts[g.start:g.stop]
+        offs = np.concatenate([[0], np.cumsum([(a.size + 255) & ~255 for a, _ in part])])
+        slab = cache.get("slab")
+        if slab is None or slab.device != dev or slab.numel() < int(offs[-1]):
+            cache.pop("slab", None)
+            slab = cache["slab"] = torch.empty(int(offs[-1]), dtype=torch.uint8, device=dev)
+        pk = [codec._sign_upload(a, h, dev, out=slab[int(o): int(o) + a.size])
+              for (a, h), o in zip(part, offs)]
+        if wts is None:
+            gar.aggregate_packets(pk, out=out)
+        else:
+            codec.fold_sign(pk, [float(x) for x in wts[g.start:g.stop]], out=out, continue_sum=gi > 0)
+    return out
+
+
 def aggregate_grads(self, clients: List, input_feature: np.ndarray = None,
                     val_loader=None) -> None:
     """aggregation.py:54-78 on the device: sets ``self.agg_grad`` (host array) and
@@ -646,6 +795,9 @@ def aggregate_grads(self, clients: List, input_feature: np.ndarray = None,
         raise NotImplementedError("pc_analysis (randomized SVD of G) is outside the hot path")
     # Krum / pc_analysis "gram": a round outside the route's conditions raises here, before a
     # GPU is touched (no dense fallback)
+    # a round of 'sign' clients: its own route, or NotImplementedError for a scheme without a
+    # consumer of sign packets (before the gram route's own conditions are read)
+    sign = sign_route(self, clients)
     k_gram = gram_route_k(self, clients) if gram_wanted(self) else None
     dev = _device_of(self)
     grad0 = np.asarray(clients[0].grad)
@@ -657,6 +809,12 @@ def aggregate_grads(self, clients: List, input_feature: np.ndarray = None,
         self.agg_path = "gram"
         self.curr_G = None
         self.agg_grad = gram_round(self, clients, n, k_gram, dev).cpu().numpy()
+        return
+    if sign:
+        # every client a scaled-sign packet: encoded one at a time, folded or voted from the bits
+        self.agg_path = "sign"
+        self.curr_G = None
+        self.agg_grad = sign_round(self, clients, n, dev).cpu().numpy()
         return
     k_ef = ef_batch_k(self, clients)
     if k_ef is not None:
@@ -802,6 +960,10 @@ def aggregate_wire(self, payloads, n: Optional[int] = None) -> None:
       ``coordinate_median`` and
       ``pc_analysis: "gram"``: at most ``FC_GRAM_MAX_M`` payloads, all resident within the budget;
       ``codec.gram`` then ``gar.aggregate_packets`` exactly as the "gram" route does.
+    * payloads that all carry the sign magic (``Compression.compress_wire`` of 'sign' clients):
+      validated by ``fc_sign_wire_validate``, uploaded and folded in groups (``fed_avg``,
+      ``codec.fold_sign``) or voted over, all resident (``sign_majority``), with ``agg_path =
+      "wire-sign"``; the other schemes and a round that mixes the two payload kinds raise.
     Hierarchies, payloads of differing n and a round that does not fit raise
     ``NotImplementedError`` naming the condition."""
     no = _wire_no
@@ -814,11 +976,42 @@ def aggregate_wire(self, payloads, n: Optional[int] = None) -> None:
     if self.num_hierarchies != 0:
         no("no hierarchies (num_hierarchies == 0)")
     gar = self.gar
+    cfg = getattr(self, "aggregation_config", None) or {}
+    kinds = [codec.is_sign_payload(raw) for raw in payloads]
+    if any(kinds):
+        # ---- a round of sign payloads: validated on the host, folded or voted ("wire-sign") ----
+        if not all(kinds):
+            no("payloads of one kind (the round mixes sign packets and 'top' wire packets)")
+        if type(gar) not in (FedAvg, SignMajority) or gram_wanted(self):
+            no("fed_avg or sign_majority for sign packets (Krum, the linear rules, the trim rules "
+               "and pc_analysis 'gram' have no consumer of sign packets)")
+        if cfg.get("devices", DEFAULT_DEVICES) not in (None, 1):
+            no("one device")
+        w = getattr(gar, "gradient_weights", None)
+        if w is not None and type(gar) is SignMajority:
+            raise ValueError("SignMajority is unweighted: gradient_weights must be None")
+        if w is not None and np.asarray(w).dtype != np.float32:
+            no("float32 GAR weights")
+        hosts = []
+        for i, raw in enumerate(payloads):
+            try:
+                a, h = codec._sign_check(raw)
+            except ValueError as e:
+                raise ValueError(f"payload {i}: {e}") from None
+            hn = int(h.pkt.n)
+            if n is None:
+                n = hn
+            if hn != int(n):
+                no(f"payloads of one length n (payload {i} has n = {hn}, not {int(n)})")
+            hosts.append((a, h))
+        self.agg_path = "wire-sign"
+        self.curr_G = None
+        self.agg_grad = sign_wire_round(self, hosts, int(n), _device_of(self)).cpu().numpy()
+        return
     family = gram_wanted(self)
     if not family and type(gar) is not FedAvg:
         no("the device FedAvg, Krum, spectral_gram, geometric_median, centered_clip, trimmed_mean "
            "or coordinate_median")
-    cfg = getattr(self, "aggregation_config", None) or {}
     if cfg.get("devices", DEFAULT_DEVICES) not in (None, 1):
         no("one device")
     w = getattr(gar, "gradient_weights", None)
@@ -918,7 +1111,7 @@ class Aggregator:
         self.gar = self.__get_gar()
         self.curr_G = None
         self.agg_grad = None
-        self.agg_path = None                # "stream" | "dense-fold" | "dense" | "ef-batch" | "gram" | "wire" | "wire-fold": the last call's path
+        self.agg_path = None                # "stream" | "dense-fold" | "dense" | "ef-batch" | "gram" | "sign" | "wire" | "wire-fold" | "wire-sign": the last call's path
         self.agg_draws = None               # streamed np.random draws: "device-mt" | "device-perm" | "host" | None
         self.analyze_pc = self.aggregation_config.get("pc_analysis", False)
         self.num_hierarchies = self.aggregation_config.get("num_hierarchies", 0)
@@ -943,6 +1136,8 @@ class Aggregator:
             return TrimmedMean(aggregation_config=self.aggregation_config)
         if scheme == "coordinate_median":
             return CoordinateMedian(aggregation_config=self.aggregation_config)
+        if scheme == "sign_majority":
+            return SignMajority(aggregation_config=self.aggregation_config)
         if scheme == "fed_spectral_avg":
             raise NotImplementedError("SpectralFedAvg is outside the codec hot path (DESIGN.md §8)")
         raise NotImplementedError

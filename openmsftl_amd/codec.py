@@ -12,6 +12,9 @@
     w   = pack(pkt); raw = w.tobytes()     # the compact wire form: the kept entries alone
     pkt = unpack(wire_from_host(raw))      # validated host bytes back into a slotted packet
     agg = fold_wire(wires, w)              # decode_accumulate(unpack(wires), w) without the unpack
+    pkt, e2 = encode_sign(g, e)            # 1 bit per coordinate and one scale, e2 = a - q
+    agg = fold_sign(pkts, w)               # FedAVG of sign packets, the dense fold's bits
+    v   = vote_sign(pkts, eta)             # majority vote: -eta / +eta / +0.0 per coordinate
 
 Packets live on the GPU in the slotted layout of include/fedcodec.h: chunk c (8192 elements)
 lists its entries, ascending, at ``[c*8192, c*8192 + cnt[c])`` of ``idx``/``val`` (or
@@ -1137,19 +1140,24 @@ def wire_from_host(data, n: Optional[int] = None, device=None) -> WirePacket:
     return _wire_upload(*_wire_check(data, n), device)
 
 
-def _wire_check(data, n: Optional[int] = None):
-    """fc_wire_validate on host bytes: (the bytes as a uint8 array, their ``L.WireHdr``), or
-    ``ValueError`` with the library's reason.  Touches no device."""
+def _host_bytes(data) -> np.ndarray:
+    """Host bytes (``bytes``, a 1-D NumPy uint8 array or a 1-D CPU uint8 tensor) as a contiguous
+    uint8 array, without a copy where none is needed."""
     if isinstance(data, torch.Tensor):
         if data.is_cuda or data.dtype != torch.uint8 or data.dim() != 1:
             raise TypeError("data must be bytes, a 1-D NumPy uint8 array or a 1-D CPU uint8 tensor")
-        arr = data.contiguous().numpy()
-    elif isinstance(data, (bytes, bytearray, memoryview)):
-        arr = np.frombuffer(data, dtype=np.uint8)
-    elif isinstance(data, np.ndarray) and data.dtype == np.uint8 and data.ndim == 1:
-        arr = np.ascontiguousarray(data)
-    else:
-        raise TypeError("data must be bytes, a 1-D NumPy uint8 array or a 1-D CPU uint8 tensor")
+        return data.contiguous().numpy()
+    if isinstance(data, (bytes, bytearray, memoryview)):
+        return np.frombuffer(data, dtype=np.uint8)
+    if isinstance(data, np.ndarray) and data.dtype == np.uint8 and data.ndim == 1:
+        return np.ascontiguousarray(data)
+    raise TypeError("data must be bytes, a 1-D NumPy uint8 array or a 1-D CPU uint8 tensor")
+
+
+def _wire_check(data, n: Optional[int] = None):
+    """fc_wire_validate on host bytes: (the bytes as a uint8 array, their ``L.WireHdr``), or
+    ``ValueError`` with the library's reason.  Touches no device."""
+    arr = _host_bytes(data)
     if n is not None and int(n) < 1:
         raise ValueError("n must be at least 1")
     lib = L.load()
@@ -1308,6 +1316,226 @@ def div_scalar(x: torch.Tensor, d: float) -> torch.Tensor:
     L.check(lib.fc_div_scalar(_vp(x), x.numel(), ctypes.c_float(d), _stream(x.device)),
             "fc_div_scalar")
     return x
+
+
+# ---- scaled sign with error feedback (opt-in, no reference counterpart; csrc/fc_sign.hip) ------
+@dataclass
+class SignPacket:
+    """A scaled-sign packet in HBM (include/fedcodec.h): n sign bits, bit ``t % 32`` of word
+    ``t // 32``, and the float32 scale in the header's ``p``."""
+    words: torch.Tensor          # int32[fc_sign_words(n)] (uint32 payload), 16-byte aligned
+    hdr: torch.Tensor            # uint8[HDR_BYTES]
+    n: int
+    fmt: int = L.FC_FMT_SIGN
+    buf: Optional[torch.Tensor] = None     # sign_from_host: the uploaded payload both live in
+
+    @classmethod
+    def alloc(cls, n: int, device) -> "SignPacket":
+        if n < 1:
+            raise ValueError("a sign packet needs n >= 1")
+        words = int(L.load().fc_sign_words(n))
+        return cls(torch.empty(words, dtype=_U32, device=device),
+                   torch.empty(L.HDR_BYTES, dtype=torch.uint8, device=device), n)
+
+    def view(self, weight: float = 1.0) -> L.PacketView:
+        return L.PacketView(idx=0, val=0, bitmap=self.words.data_ptr(), cnt=0,
+                            hdr=self.hdr.data_ptr(), qoff=0, weight=float(np.float32(weight)),
+                            reserved=0)
+
+    def header(self) -> L.PacketHdr:
+        """Synchronous D2H read of the device header."""
+        return L.PacketHdr.from_buffer_copy(self.hdr.cpu().numpy().tobytes())
+
+    def scale(self) -> np.float32:
+        """The packet's scale s (synchronises)."""
+        return np.float32(self.header().p)
+
+
+_SIGN_WS = {}
+
+
+def _check_sign_packets(packets) -> list:
+    pk = list(packets)
+    if not pk:
+        raise ValueError("no packets")
+    if not all(isinstance(p, SignPacket) for p in pk):
+        raise TypeError("sign packets expected (codec.encode_sign, codec.sign_from_host)")
+    n, dev = pk[0].n, pk[0].words.device
+    need = int(L.load().fc_sign_words(n))
+    for p in pk:
+        if p.n != n or p.words.device != dev:
+            raise ValueError("packets must share n and the device")
+        if p.words.dtype != _U32 or p.words.numel() < need or p.words.data_ptr() % 16:
+            raise ValueError("a sign packet's words must be 16-byte aligned int32[fc_sign_words(n)]")
+    return pk
+
+
+def encode_sign(g: torch.Tensor, residual: Optional[torch.Tensor] = None,
+                residual_out: Optional[torch.Tensor] = None, *,
+                packet: Optional[SignPacket] = None):
+    """The scaled-sign packet of ``a = fl32(g + residual)`` (``a = g`` without a residual):
+    ``s = fl32(sum |a| / n)`` in float64 in a fixed order and the sign bits of ``a``
+    (fc_sign_encode: a norm pass and a streaming pass, no synchronisation).  With ``residual`` or
+    ``residual_out`` given it also writes the new residual ``e' = fl32(a - q)``, ``q = +-s`` (into
+    ``residual_out``, which may not overlap ``g`` or ``residual``; allocated when None).
+    Returns ``(packet, new residual or None)``."""
+    lib = L.load()
+    _require_cuda_f32(g)
+    n, dev = g.numel(), g.device
+    if n < 1:
+        raise ValueError("encode_sign needs n >= 1")
+    want = residual is not None or residual_out is not None
+    for name, t in (("residual", residual), ("residual_out", residual_out)):
+        if t is not None:
+            _require_cuda_f32(t, name)
+            if t.numel() != n or t.device != dev:
+                raise ValueError(f"{name} must have g's length and device")
+    if want and residual_out is None:
+        residual_out = torch.empty(n, dtype=torch.float32, device=dev)
+    if packet is None:
+        packet = SignPacket.alloc(n, dev)
+    elif packet.n != n or packet.words.device != dev:
+        raise ValueError("packet must have g's length and device")
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(),
+           torch.cuda.current_stream(dev).cuda_stream)        # k_sign_norm's ticket: per stream
+    ws = _SIGN_WS.get(key)
+    if ws is None:
+        ws = _SIGN_WS[key] = torch.zeros(int(lib.fc_sign_workspace_bytes(n)), dtype=torch.uint8,
+                                         device=dev)
+    L.check(lib.fc_sign_encode(_vp(g), _vp(residual), _vp(residual_out), n, _vp(packet.words),
+                               packet.words.numel(), _vp(packet.hdr), _vp(ws), ws.numel(),
+                               _stream(dev)), "fc_sign_encode")
+    return packet, residual_out
+
+
+def decode_sign(packet: SignPacket, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The dense ``q = +-s`` of a sign packet (fc_sign_decode)."""
+    (packet,) = _check_sign_packets([packet])
+    dev = packet.words.device
+    if out is None:
+        out = torch.empty(packet.n, dtype=torch.float32, device=dev)
+    _require_cuda_f32(out, "out")
+    if out.numel() != packet.n:
+        raise ValueError("out must have n elements")
+    v = packet.view()
+    L.check(L.load().fc_sign_decode(ctypes.byref(v), packet.n, _vp(out), _stream(dev)),
+            "fc_sign_decode")
+    return out
+
+
+def _sign_views(pk, weights, dev) -> torch.Tensor:
+    arr = (L.PacketView * len(pk))(*[p.view(float(w)) for p, w in zip(pk, weights)])
+    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
+
+
+def fold_sign(packets: Sequence[SignPacket], weights, out: Optional[torch.Tensor] = None,
+              continue_sum: bool = False) -> torch.Tensor:
+    """FedAVG straight from sign packets (fc_sign_fold): the bits of :func:`weighted_sum_dense`
+    on the rows :func:`decode_sign` gives, reading N/8 bytes per client.  ``continue_sum=True``
+    folds into the partial sum already in ``out``."""
+    pk = _check_sign_packets(packets)
+    weights = [float(x) for x in weights]
+    if len(weights) != len(pk):
+        raise ValueError("one weight per packet")
+    n, dev = pk[0].n, pk[0].words.device
+    if out is None:
+        if continue_sum:
+            raise ValueError("continue_sum needs the partial sum in `out`")
+        out = torch.empty(n, dtype=torch.float32, device=dev)
+    _require_cuda_f32(out, "out")
+    if out.numel() != n:
+        raise ValueError("out must have n elements")
+    L.check(L.load().fc_sign_fold(_vp(_sign_views(pk, weights, dev)), len(pk), n, _vp(out),
+                                  int(bool(continue_sum)), _stream(dev)), "fc_sign_fold")
+    return out
+
+
+def vote_sign(packets: Sequence[SignPacket], eta: float,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The majority vote over sign packets (fc_sign_vote): ``-eta`` where more than half of the
+    clients send a set bit, ``+eta`` where fewer do, ``+0.0`` on a tie.  Scales and weights play
+    no part."""
+    pk = _check_sign_packets(packets)
+    n, dev = pk[0].n, pk[0].words.device
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=dev)
+    _require_cuda_f32(out, "out")
+    if out.numel() != n:
+        raise ValueError("out must have n elements")
+    L.check(L.load().fc_sign_vote(_vp(_sign_views(pk, [1.0] * len(pk), dev)), len(pk), n,
+                                  ctypes.c_float(float(np.float32(eta))), _vp(out), _stream(dev)),
+            "fc_sign_vote")
+    return out
+
+
+def sign_wire_bytes(n: int) -> int:
+    """The size of a sign packet's wire form: 128 + 4 fc_sign_words(n)."""
+    return L.WIRE_HDR_BYTES + 4 * int(L.load().fc_sign_words(n))
+
+
+def pack_sign(packet: SignPacket) -> torch.Tensor:
+    """The wire form of a sign packet as a device uint8 tensor (include/fedcodec.h): the 32 fixed
+    bytes, the device header and the words, three copies and no kernel, no synchronisation."""
+    (packet,) = _check_sign_packets([packet])
+    dev = packet.words.device
+    words = int(L.load().fc_sign_words(packet.n))
+    total = L.WIRE_HDR_BYTES + 4 * words
+    fixed = np.zeros(32, dtype=np.uint8)
+    fixed[:8].view(np.uint32)[:] = (L.SIGN_MAGIC, 1)
+    fixed[8:16].view(np.uint64)[0] = total
+    buf = torch.empty(total, dtype=torch.uint8, device=dev)
+    buf[:32].copy_(torch.from_numpy(fixed))
+    buf[32:L.WIRE_HDR_BYTES].copy_(packet.hdr)
+    buf[L.WIRE_HDR_BYTES:].copy_(packet.words[:words].view(torch.uint8))
+    return buf
+
+
+def is_sign_payload(data) -> bool:
+    """Do these host bytes start with the sign packet's magic?"""
+    arr = _host_bytes(data)
+    return arr.size >= 4 and int(arr[:4].view(np.uint32)[0]) == L.SIGN_MAGIC
+
+
+def _sign_check(data, n: Optional[int] = None):
+    """fc_sign_wire_validate on host bytes: (the bytes as a uint8 array, their
+    ``L.SignWireHdr``), or ``ValueError`` with the library's reason.  Touches no device."""
+    arr = _host_bytes(data)
+    if n is not None and int(n) < 1:
+        raise ValueError("n must be at least 1")
+    lib = L.load()
+    rc = lib.fc_sign_wire_validate(ctypes.c_void_p(arr.ctypes.data), arr.size, int(n) if n else 0)
+    if rc != L.FC_OK:
+        msg = lib.fc_last_error()
+        raise ValueError(msg.decode() if msg else "sign wire: invalid packet")
+    return arr, L.SignWireHdr.from_buffer_copy(arr[: L.WIRE_HDR_BYTES].tobytes())
+
+
+def _sign_upload(arr: np.ndarray, hdr, device=None, out: Optional[torch.Tensor] = None) -> SignPacket:
+    """The H2D copy of bytes :func:`_sign_check` has passed (into ``out``, a 16-byte aligned
+    uint8 device tensor of their size, when given); the packet's header and words are views of it."""
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    if arr.flags.writeable:
+        host = torch.from_numpy(arr)
+    else:                                          # e.g. bytes: only ever read, so no host copy
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", UserWarning)
+            host = torch.frombuffer(arr, dtype=torch.uint8)
+    if out is None:
+        buf = host.to(dev)
+    else:
+        _check_wire_buffer(out, dev, "out")
+        if out.numel() != arr.size:
+            raise ValueError("out must have the payload's size")
+        buf = out.copy_(host)
+    return SignPacket(words=buf[L.WIRE_HDR_BYTES:].view(_U32), hdr=buf[32:L.WIRE_HDR_BYTES],
+                      n=int(hdr.pkt.n), buf=buf)
+
+
+def sign_from_host(data, n: Optional[int] = None, device=None) -> SignPacket:
+    """Host bytes as a :class:`SignPacket` on ``device``: ALWAYS through ``fc_sign_wire_validate``
+    first (``ValueError`` with the library's reason; no device work has started then), then the
+    H2D copy.  ``n``: the length the packet must have."""
+    return _sign_upload(*_sign_check(data, n), device)
 
 
 # ---- float64 gradients (attack_models.py:105-106 -> aggregation.py:61) ----------------------

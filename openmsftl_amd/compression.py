@@ -7,6 +7,7 @@ Same constructor keys and defaults, same ``compress(grad, layer_wise=False)`` co
   * 'dropout-biased'    float64 result                                (compression.py:47-53)
   * 'dropout-unbiased'  float64 result, fl64(g)/p                     (compression.py:55-60)
   * 'qsgd', unknown names, layer_wise=True -> NotImplementedError at call time (:24,62,76)
+  * 'sign'              opt-in, not in the reference: the scaled sign, float32 (:meth:`Compression._sign`)
 The compute runs in hand-written HIP kernels (libfedcodec.so); there is no CPU fallback.
 
 RNG: by default ('rng': 'numpy') 'rand'/'dropout-*' draw from the process-global legacy
@@ -19,7 +20,7 @@ generates ``np.random.binomial``'s own MT19937 variates on the device (jump-ahea
 (Philox4x32-10 keyed by ``'seed'``, counter advanced per call) — no host RNG work, not
 stream-identical to the reference (documented in DESIGN.md).
 
-Error feedback (opt-in key ``'error_feedback': True``, 'top' on float32 gradients only; the
+Error feedback (opt-in key ``'error_feedback': True``, 'top' and 'sign' on float32 gradients only; the
 reference keeps no state between calls): the object keeps on the device what its calls so far
 dropped and adds it to the next gradient (:meth:`Compression._top_ef`, ``get_residual`` /
 ``set_residual`` / ``reset_residual``).
@@ -113,9 +114,12 @@ class Compression:
         fn = self.compression_function
         if fn == 'full':
             return grad
+        if fn == 'sign':
+            return self._sign(grad)
         if self.error_feedback:
             if fn != 'top':
-                raise NotImplementedError(f"error_feedback is built for 'top' only (got {fn!r})")
+                raise NotImplementedError("error_feedback is built for 'top' and 'sign' only "
+                                          f"(got {fn!r})")
             return self._top_ef(grad)
         if fn == 'qsgd' and self.qsgd == 'native':
             return self._qsgd(grad)
@@ -248,16 +252,66 @@ class Compression:
         self._residual_numpy = not on_device
         return pkt
 
+    # ------------------------------------------------------------------------------------
+    def _sign(self, grad):
+        """'sign' (opt-in, not in the reference): the scaled sign of EF-signSGD (Karimireddy,
+        Rebjock, Stich, Jaggi, ICML 2019), 1 bit per coordinate and one float32 scale:
+
+            a = fl32(grad + residual)  (grad itself without error feedback);
+            s = fl32(sum |a| / n) in float64;  q = -s where a's sign bit is set, +s elsewhere;
+            residual = fl32(a - q)     (with ``"error_feedback": True`` only)
+
+        Returns the dense q as compress() returns it: a fresh float32 array of the input's kind,
+        the input untouched.  float32 gradients only.  With error feedback the residual lives on
+        the device as :meth:`_top_ef`'s does (the same two buffers, ``get_residual`` /
+        ``set_residual`` / ``reset_residual``) and advances on EVERY call.  A non-finite gradient
+        makes s inf or NaN and poisons the residual exactly as the arithmetic above says:
+        :meth:`reset_residual` starts over."""
+        on_device = isinstance(grad, torch.Tensor)
+        pkt = self._sign_packet(grad)
+        if pkt is None:                            # an empty gradient
+            return grad.clone() if on_device else np.zeros_like(grad)
+        out = codec.decode_sign(pkt)
+        return out if on_device else out.cpu().numpy()
+
+    def _sign_packet(self, grad):
+        """The packet behind :meth:`_sign` (None for an empty gradient): with error feedback the
+        residual advances here, once per call, whether the caller wants the dense q or the wire
+        form."""
+        L.load()
+        on_device = isinstance(grad, torch.Tensor)
+        g = self._to_device(grad)
+        n = g.numel()
+        if n == 0:
+            return None
+        if g.dtype != torch.float32:
+            raise NotImplementedError(f"'sign' handles float32 gradients only (got {g.dtype})")
+        if g.data_ptr() % 16:
+            g = g.clone()
+        if not self.error_feedback:
+            return codec.encode_sign(g)[0]
+        res, spare = self._ef_buffers(n, g.device)
+        pkt, new = codec.encode_sign(g, res, residual_out=spare)
+        self._ef_commit(res, new, not on_device)
+        return pkt
+
     def compress_wire(self, grad) -> bytes:
         """What a client sends instead of the dense ``compress(grad)``: the 'top' packet of a 1-D
         float32 gradient (NumPy array or CUDA tensor) in its wire form (include/fedcodec.h:
-        encode, resolve, ``codec.pack``), as ``bytes``.  With ``"error_feedback": True`` the
-        packet is :meth:`_top_ef`'s and the residual advances exactly as ``compress`` advances
-        it.  ``Aggregator.aggregate_wire`` takes a round of these.  Other codecs raise
-        ``NotImplementedError`` (``codec.pack`` itself takes any idx/val packet)."""
+        encode, resolve, ``codec.pack``), as ``bytes``; for 'sign' the sign packet's wire form
+        (``codec.pack_sign``).  With ``"error_feedback": True`` the
+        packet is :meth:`_top_ef`'s (:meth:`_sign`'s) and the residual advances exactly as
+        ``compress`` advances it.  ``Aggregator.aggregate_wire`` takes a round of these.  Other
+        codecs raise ``NotImplementedError`` (``codec.pack`` itself takes any idx/val packet)."""
         fn = self.compression_function
+        if fn == 'sign':
+            pkt = self._sign_packet(grad)
+            if pkt is None:
+                raise ValueError("compress_wire: empty gradient")
+            return codec.pack_sign(pkt).cpu().numpy().tobytes()
         if fn != 'top':
-            raise NotImplementedError(f"compress_wire is built for 'top' only (got {fn!r})")
+            raise NotImplementedError("compress_wire is built for 'top' only, and for 'sign' "
+                                      f"(got {fn!r})")
         L.load()
         if self.error_feedback:
             pkt = self._top_ef_packet(grad)

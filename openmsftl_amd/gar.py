@@ -35,6 +35,9 @@ largest of every coordinate's M values and takes the float32 mean of the rest,
 ``CoordinateMedian`` is ``b = (M - 1) // 2``.  ``aggregate_packets`` is one kernel over the
 packets (``codec.trimmed_mean``): only a column's non-zeros are ordered, no Gram matrix is
 needed, no client is excluded as a whole and the rules take no weights.
+
+``SignMajority`` is the majority vote over scaled-sign packets (``codec.vote_sign``); ``FedAvg``'s
+``aggregate_packets`` folds such packets with ``codec.fold_sign``.
 """
 from __future__ import annotations
 
@@ -95,6 +98,8 @@ class GAR:
         if w.dtype != np.float32:
             raise TypeError("aggregate_packets folds with float32 weights; float64 weights "
                             "promote G * w to float64 (use weighted_average on the dense G)")
+        if packets and isinstance(packets[0], codec.SignPacket):           # scaled-sign packets
+            return codec.fold_sign(packets, [float(x) for x in w], out=out)
         return codec.decode_accumulate(packets, [float(x) for x in w], out=out)
 
 
@@ -490,3 +495,53 @@ class CoordinateMedian(CoordinateTrim):
 
     def _trim_of(self, m: int) -> int:
         return (m - 1) // 2
+
+
+# ---- the majority vote over scaled-sign packets -------------------------------------------------
+class SignMajority(GAR):
+    """signSGD with majority vote (Bernstein, Zhao, Azizzadenesheli, Anandkumar, ICLR 2019) over
+    the clients' scaled-sign packets (``codec.vote_sign``): per coordinate ``-eta`` where more than
+    half of the clients send a set sign bit, ``+eta`` where fewer do, ``+0.0`` on a tie.  The
+    count is integer arithmetic, so the clients' order does not matter.
+
+    ``eta`` is ``aggregation_config["majority_scale"]`` when given; otherwise the median of the
+    clients' finite scales, computed in float64 on the host (``np.median``) and cast to float32
+    (no finite scale raises ``ValueError``).  ``eta`` holds the value used in the last round.
+
+    The rule is unweighted: a ``gradient_weights`` that is not None raises, as for the
+    coordinate-wise rules.  It reads sign packets alone (``aggregate_packets``, the Aggregator's
+    "sign" route): a dense G is not taken."""
+
+    def __init__(self, aggregation_config):
+        GAR.__init__(self, aggregation_config=aggregation_config)
+        scale = aggregation_config.get("majority_scale", None)
+        if scale is not None and (isinstance(scale, bool)
+                                  or not isinstance(scale, (int, float, np.floating, np.integer))):
+            raise ValueError(f"majority_scale must be a number (got {scale!r})")
+        self.majority_scale = None if scale is None else np.float32(scale)
+        self.eta = None
+
+    def _eta_of(self, scales) -> np.float32:
+        """eta for a round whose clients sent these scales."""
+        if self.majority_scale is not None:
+            return self.majority_scale
+        s = np.asarray(scales, dtype=np.float64)
+        s = s[np.isfinite(s)]
+        if s.size == 0:
+            raise ValueError("sign_majority: no client sent a finite scale (give majority_scale)")
+        return np.float32(np.median(s))
+
+    def aggregate(self, G, client_ids=None):
+        raise NotImplementedError("SignMajority reads the clients' sign packets (aggregate_packets, "
+                                  "the Aggregator's sign route); a dense G is not taken")
+
+    def aggregate_packets(self, packets: Sequence["codec.SignPacket"], out=None) -> torch.Tensor:
+        if self.gradient_weights is not None:
+            raise ValueError("SignMajority is unweighted: gradient_weights must be None")
+        packets = list(packets)
+        if not packets or not all(isinstance(p, codec.SignPacket) for p in packets):
+            raise TypeError("SignMajority votes over sign packets (codec.encode_sign)")
+        scales = ([] if self.majority_scale is not None
+                  else [h.p for h in codec.headers(packets)])
+        self.eta = self._eta_of(scales)
+        return codec.vote_sign(packets, float(self.eta), out=out)
