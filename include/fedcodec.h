@@ -584,6 +584,55 @@ int fc_sign_vote(const fc_packet_view* views_dev, int m, uint64_t n, float eta, 
 int fc_sign_wire_validate(const void* host_bytes, size_t len, uint64_t n_expected /* 0 = any */);
 int fc_sign_fold_form(int form);
 
+/* ---- The clients' geometry from scaled-sign packets: Gram matrix and G v (fc_sign_gram.hip) ----
+ * What fc_packets_gram and fc_packets_dot give for idx/val packets, for a round of sign packets,
+ * so that Krum, the linear rules and pc_analysis "gram" can take 1-bit clients.  With
+ * d_i[t] = b_i[t] ? -s_i : +s_i (the row fc_sign_decode makes):
+ *   <d_i, d_j> = s_i s_j (n - 2 H_ij),  H_ij = popcount(words_i XOR words_j)
+ *   <d_i, v>   = s_i D_i,               D_i  = sum_t (b_i[t] ? -v[t] : +v[t])
+ * views_dev: DEVICE array of m FC_FMT_SIGN views, as fc_sign_fold takes them: the words in
+ *   `bitmap`, 16-B aligned, with zero bits at and past n and zero pad words (the encoder's and the
+ *   validator's guarantee); s_i is the float32 scale in the packet header's p; `weight` is ignored.
+ *   1 <= m <= FC_GRAM_MAX_M, 1 <= n < 2^32.
+ * fc_sign_gram: H_ij is the exact integer count of differing bits among the first n.
+ *   gram[i*m + j] = fl64((fl64(s_i) * fl64(s_j)) * (double)(n - 2 H_ij)): the first product is
+ *   exact (48 significant bits), the integer is exact (below 2^32 in magnitude), so the entry is
+ *   ONE IEEE float64 multiply: the correctly rounded value of the true inner product of the decoded
+ *   rows, whatever the order of anything.  The diagonal is s_i^2 n (H_ii = 0).  gram: DEVICE
+ *   float64[m*m], row-major, 16-B aligned; symmetric bit for bit (one triangle is computed and
+ *   mirrored); two calls, or any permutation of workgroups, give the same bits.
+ *   Non-finite rule: a client whose s_i is NaN or +-inf gets gram[i][*] = gram[*][i] = NaN, the
+ *   diagonal included (the rule of fc_packets_gram); every other client is unaffected.  s_i == 0
+ *   follows plain IEEE: zeros of either sign.
+ * fc_sign_dot: out[i] = fl64(s_i) * D_i for i < m, D_i summed in float64 from +0.0 over
+ *   (b_i[t] ? -(double)v[t] : +(double)v[t]); with v == NULL (the all-ones vector) D_i =
+ *   (double)(n - 2 popcount_i) exactly.  out[m] = sum_t (double)v[t]^2 (exactly (double)n when v
+ *   is NULL), as fc_packets_dot defines it.  v: DEVICE float32[n], 16-B aligned, or NULL; out:
+ *   DEVICE float64[m + 1], 16-B aligned.
+ *   Non-finite rule: a non-finite s_i gives out[i] = NaN; a non-finite element in v makes all
+ *   m + 1 outputs NaN.
+ *   Determinism: the order of summation is a function of n and m alone: the grid and each
+ *   workgroup's range of words come from them, every thread adds its coordinates in index order,
+ *   the partial sums go to the workspace and a second launch adds them in index order.
+ * Both: stream-ordered; no allocation, no host synchronisation; no floating-point atomics; no
+ *   workgroup waits in-kernel for another (no fc_fused_order_* handling).  The Gram's integer
+ *   counts are added inside a workgroup with integer LDS atomics (any order, the same integers)
+ *   and across workgroups by a finishing launch.  ws: fc_sign_gram_workspace_bytes(n, m) /
+ *   fc_sign_dot_workspace_bytes(n, m) bytes (monotone in n and m), 16-B aligned, NO one-time
+ *   zeroing: every word a call reads it has written first.
+ * Argument errors return before the GPU is touched: FC_ERR_ARG for a NULL views_dev, gram / out or
+ *   ws, m < 1 or m > FC_GRAM_MAX_M, n == 0 (or n >= 2^32), a gram, v, out or ws that is not 16-B
+ *   aligned; FC_ERR_WORKSPACE for a short workspace. */
+size_t fc_sign_gram_workspace_bytes(uint64_t n, int m);
+int fc_sign_gram(const fc_packet_view* views_dev, int m, uint64_t n,
+                 double* gram /* DEVICE float64[m*m], row-major, 16-B aligned */,
+                 void* ws, size_t ws_bytes, fc_stream_t stream);
+size_t fc_sign_dot_workspace_bytes(uint64_t n, int m);
+int fc_sign_dot(const fc_packet_view* views_dev, int m, uint64_t n,
+                const float* v /* DEVICE float32[n], 16-B aligned, or NULL = all ones */,
+                double* out /* DEVICE float64[m + 1], 16-B aligned */,
+                void* ws, size_t ws_bytes, fc_stream_t stream);
+
 /* ---- float64 gradients ------------------------------------------------------------
  * The reference reaches the codec with float64 gradients after RandomGaussian with
  * noise_scale == 0 (attack_models.py:105-106); G takes that dtype (aggregation.py:61) and

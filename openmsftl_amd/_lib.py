@@ -163,6 +163,10 @@ SIGNATURES = {
     "fc_sign_vote": (_i32, [_vp, _i32, _u64, ctypes.c_float, _vp, _vp]),
     "fc_sign_wire_validate": (_i32, [_vp, _sz, _u64]),
     "fc_sign_fold_form": (_i32, [_i32]),
+    "fc_sign_gram_workspace_bytes": (_sz, [_u64, _i32]),
+    "fc_sign_gram": (_i32, [_vp, _i32, _u64, _vp, _vp, _sz, _vp]),
+    "fc_sign_dot_workspace_bytes": (_sz, [_u64, _i32]),
+    "fc_sign_dot": (_i32, [_vp, _i32, _u64, _vp, _vp, _vp, _sz, _vp]),
     "fc_topk_dense_f64": (_i32, [_vp, _u64, _u64, _i32, _u64, _u64, _vp, _vp, _sz, _vp]),
     "fc_topk_dense_f64_sampled": (_i32, [_vp, _u64, _u64, _vp, _vp, _sz, _vp, _vp]),
     "fc_mask_dense_f64": (_i32, [_vp, _u64, _i32, _vp, _dbl, _u64, _u64, _vp, _vp]),

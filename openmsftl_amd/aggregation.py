@@ -615,19 +615,22 @@ def gram_round(agg, clients, n: int, k: int, dev: torch.device) -> torch.Tensor:
 
 
 def _gram_family(agg, gar, pk) -> torch.Tensor:
-    """The "gram" route's consumers on a round's resident packets (also aggregate_wire's)."""
+    """The "gram" route's consumers on a round's resident packets (also aggregate_wire's, and
+    the "sign-gram" routes' on sign packets: ``codec.gram_sign`` and ``codec.fold_sign``)."""
     m = len(pk)
     pc = getattr(agg, "analyze_pc", False) == "gram"
+    sign = isinstance(pk[0], codec.SignPacket)
     if isinstance(gar, CoordinateTrim):
         out = gar.aggregate_packets(pk)
         gram = codec.gram(pk) if pc else None
     else:
-        gram = codec.gram(pk)
+        gram = codec.gram_sign(pk) if sign else codec.gram(pk)
         if isinstance(gar, (Krum, LinearRule)):
             out = gar.aggregate_packets(pk, gram=gram)
         else:
             w = gar._weights(m, np.float32)                         # gar.py:37-42 (persisted)
-            out = codec.decode_accumulate(pk, [float(x) for x in w])
+            fold = codec.fold_sign if sign else codec.decode_accumulate
+            out = fold(pk, [float(x) for x in w])
     if pc:
         gar.Sigma_tracked.append(gram_singular_values(gram.cpu().numpy()))
     return out
@@ -651,7 +654,8 @@ def sign_route(agg, clients) -> bool:
     outside these conditions answers False (the generic routes take it); a ``sign_majority`` round
     outside them raises ``NotImplementedError`` naming the condition, and so does a round of 'sign'
     clients under a scheme that has no consumer of sign packets (Krum, the linear rules, the trim
-    rules, ``pc_analysis: "gram"``).  Touches no GPU (the budget is checked here only when
+    rules, ``pc_analysis: "gram"``) unless ``"sign_geometry"`` is set and the scheme is one of
+    :func:`sign_geometry_wanted` (then False: :func:`sign_gram_route` decides).  Touches no GPU (the budget is checked here only when
     ``device_budget_bytes`` is configured; :func:`sign_round` checks the default budget)."""
     gar = getattr(agg, "gar", None)
     cfg = getattr(agg, "aggregation_config", None) or {}
@@ -662,6 +666,8 @@ def sign_route(agg, clients) -> bool:
             _sign_no("every client to compress with 'sign'")
         return False
     if gram_wanted(agg):
+        if sign_geometry_wanted(agg):
+            return False                       # the "sign-gram" route's business (sign_gram_route)
         what = type(gar).__name__ if type(gar) is not FedAvg else "pc_analysis 'gram'"
         raise NotImplementedError(f"{what} has no consumer of sign packets: a round of 'sign' "
                                   "clients takes fed_avg or sign_majority")
@@ -747,6 +753,123 @@ def sign_round(agg, clients, n: int, dev: torch.device) -> torch.Tensor:
     return out
 
 
+# ---- the "sign-gram" route (opt-in): the Gram family's consumers on a round of sign packets ----
+def sign_geometry_wanted(agg) -> bool:
+    """Is ``aggregation_config["sign_geometry"]`` set and the scheme one whose geometry sign
+    packets can give: Krum, a linear rule, or the device FedAvg with ``pc_analysis: "gram"``?
+    (The coordinate-wise rules have no kernel over sign packets.)"""
+    cfg = getattr(agg, "aggregation_config", None) or {}
+    return (bool(cfg.get("sign_geometry", False)) and gram_wanted(agg)
+            and not isinstance(agg.gar, CoordinateTrim))
+
+
+def sign_gram_resident_bytes(n: int, m: int, packets_bytes: Optional[int] = None) -> int:
+    """Device bytes the "sign-gram" routes hold at once: the m packets (``packets_bytes``: the
+    uploaded payloads of ``aggregate_wire``), the aggregate, a carried vector (centered_clip),
+    the Gram and dot kernels' workspaces and the Gram matrix."""
+    lib = L.load()
+    if packets_bytes is None:
+        packets_bytes = m * sign_packet_bytes(n)
+    return (packets_bytes + 4 * n + 4 * n + int(lib.fc_sign_gram_workspace_bytes(n, m))
+            + int(lib.fc_sign_dot_workspace_bytes(n, m)) + 8 * m * m)
+
+
+def sign_gram_route(agg, clients) -> bool:
+    """Does this round take the "sign-gram" route?  False without the key, under a scheme outside
+    :func:`sign_geometry_wanted`, or when not every client compresses with 'sign' (the other
+    routes decide).  Otherwise the conditions of :func:`sign_route`, at most ``FC_GRAM_MAX_M``
+    clients and, when ``device_budget_bytes`` is configured, the resident bytes within it: each
+    failure is a ``NotImplementedError`` naming the condition.  Touches no GPU."""
+    if not sign_geometry_wanted(agg):
+        return False
+    if not all(getattr(c.C, "compression_function", None) == "sign" for c in clients):
+        return False
+
+    def no(why: str):
+        raise NotImplementedError(f"the sign-gram route (sign_geometry) needs {why}")
+
+    cfg = getattr(agg, "aggregation_config", None) or {}
+    if not all(isinstance(c.C, Compression) for c in clients):
+        no("every client to be the drop-in Compression")
+    if agg.num_hierarchies != 0:
+        no("no hierarchies (num_hierarchies == 0)")
+    if cfg.get("devices", DEFAULT_DEVICES) not in (None, 1):
+        no("one device")
+    w = getattr(agg.gar, "gradient_weights", None)
+    if w is not None and np.asarray(w).dtype != np.float32:
+        no("float32 GAR weights")
+    n = None
+    for c in clients:
+        g = np.asarray(c.grad)
+        if g.ndim != 1 or g.dtype != np.float32:
+            no("1-D float32 gradients")
+        if n is not None and g.shape[0] != n:
+            no("gradients of one length")
+        n = g.shape[0]
+    if n == 0:
+        no("a gradient length n > 0")
+    m = len(clients)
+    if m > L.FC_GRAM_MAX_M:
+        no(f"at most {L.FC_GRAM_MAX_M} clients (got {m})")
+    b = cfg.get("device_budget_bytes")
+    if b and sign_gram_resident_bytes(n, m) > int(b):
+        no(f"the round's packets to fit device_budget_bytes ({sign_gram_resident_bytes(n, m)} > "
+           f"{int(b)} bytes)")
+    return True
+
+
+def sign_gram_round(agg, clients, n: int, dev: torch.device) -> torch.Tensor:
+    """One round on the "sign-gram" route: the clients are uploaded and encoded one at a time as
+    in :func:`sign_round` (with error feedback each residual advances exactly once), all M packets
+    stay resident, then the "gram" route's consumers run on them (:func:`_gram_family`)."""
+    m = len(clients)
+    need, budget = sign_gram_resident_bytes(n, m), _budget(agg, dev)
+    if need > budget:
+        raise NotImplementedError("the sign-gram route (sign_geometry) needs the round's packets to "
+                                  f"fit device_budget_bytes ({need} > {budget} bytes)")
+    for c in clients:                          # every residual checked before one advances
+        if c.C.error_feedback:
+            c.C._ef_buffers(n, dev, allocate=False)
+    cache = agg.__dict__.setdefault("_sign_packets", {})
+    slots = cache.get((n, dev))
+    if slots is None or len(slots) < m:
+        cache.clear()
+        slots = cache[(n, dev)] = [codec.SignPacket.alloc(n, dev) for _ in range(m)]
+    pk = slots[:m]
+    for c, slot in zip(clients, pk):
+        g = torch.from_numpy(np.ascontiguousarray(c.grad)).to(dev)
+        if c.C.error_feedback:
+            res, spare = c.C._ef_buffers(n, dev)
+            _, new = codec.encode_sign(g, res, residual_out=spare, packet=slot)
+            c.C._ef_commit(res, new, True)
+        else:
+            codec.encode_sign(g, packet=slot)
+    return _gram_family(agg, agg.gar, pk)
+
+
+def _sign_wire_upload(agg, part, dev: torch.device) -> list:
+    """Validated sign payloads (``codec._sign_check``'s pairs) into one cached device slab, 256-byte
+    aligned each: the packets are views of it."""
+    cache = agg.__dict__.setdefault("_sign_wire", {})
+    offs = np.concatenate([[0], np.cumsum([(a.size + 255) & ~255 for a, _ in part])])
+    slab = cache.get("slab")
+    if slab is None or slab.device != dev or slab.numel() < int(offs[-1]):
+        cache.pop("slab", None)
+        slab = cache["slab"] = torch.empty(int(offs[-1]), dtype=torch.uint8, device=dev)
+    return [codec._sign_upload(a, h, dev, out=slab[int(o): int(o) + a.size])
+            for (a, h), o in zip(part, offs)]
+
+
+def sign_wire_gram_round(agg, hosts, n: int, dev: torch.device) -> torch.Tensor:
+    """aggregate_wire's round of validated sign payloads under ``sign_geometry``: all uploaded,
+    then the "gram" route's consumers on them (:func:`_gram_family`)."""
+    total = sum((a.size + 255) & ~255 for a, _ in hosts)
+    need, budget = sign_gram_resident_bytes(n, len(hosts), total), _budget(agg, dev)
+    if need > budget:
+        _wire_no(f"the round's sign packets to fit device_budget_bytes ({need} > {budget} bytes)")
+    return _gram_family(agg, agg.gar, _sign_wire_upload(agg, hosts, dev))
+
+
 def sign_wire_round(agg, hosts, n: int, dev: torch.device) -> torch.Tensor:
     """aggregate_wire's round of validated sign payloads (``hosts``: what ``codec._sign_check``
     returned for each): uploaded into one cached device slab and folded in groups
@@ -764,17 +887,9 @@ def sign_wire_round(agg, hosts, n: int, dev: torch.device) -> torch.Tensor:
     else:
         groups = wire_fold_groups(sizes, n, budget)
         wts = gar._weights(m, np.float32)                               # gar.py:37-42 (persisted)
-    cache = agg.__dict__.setdefault("_sign_wire", {})
     out = torch.empty(n, dtype=torch.float32, device=dev)
     for gi, g in enumerate(groups):
-        part = hosts[g.start:g.stop]
-        offs = np.concatenate([[0], np.cumsum([(a.size + 255) & ~255 for a, _ in part])])
-        slab = cache.get("slab")
-        if slab is None or slab.device != dev or slab.numel() < int(offs[-1]):
-            cache.pop("slab", None)
-            slab = cache["slab"] = torch.empty(int(offs[-1]), dtype=torch.uint8, device=dev)
-        pk = [codec._sign_upload(a, h, dev, out=slab[int(o): int(o) + a.size])
-              for (a, h), o in zip(part, offs)]
+        pk = _sign_wire_upload(agg, hosts[g.start:g.stop], dev)
         if wts is None:
             gar.aggregate_packets(pk, out=out)
         else:
@@ -798,7 +913,9 @@ def aggregate_grads(self, clients: List, input_feature: np.ndarray = None,
     # a round of 'sign' clients: its own route, or NotImplementedError for a scheme without a
     # consumer of sign packets (before the gram route's own conditions are read)
     sign = sign_route(self, clients)
-    k_gram = gram_route_k(self, clients) if gram_wanted(self) else None
+    # opt-in ("sign_geometry"): the Gram family's consumers on a round of sign packets
+    sign_gram = sign_gram_route(self, clients)
+    k_gram = gram_route_k(self, clients) if gram_wanted(self) and not sign_gram else None
     dev = _device_of(self)
     grad0 = np.asarray(clients[0].grad)
     n = grad0.shape[0]
@@ -809,6 +926,12 @@ def aggregate_grads(self, clients: List, input_feature: np.ndarray = None,
         self.agg_path = "gram"
         self.curr_G = None
         self.agg_grad = gram_round(self, clients, n, k_gram, dev).cpu().numpy()
+        return
+    if sign_gram:
+        # every client a scaled-sign packet, all resident: Gram matrix from the bits, then the rule
+        self.agg_path = "sign-gram"
+        self.curr_G = None
+        self.agg_grad = sign_gram_round(self, clients, n, dev).cpu().numpy()
         return
     if sign:
         # every client a scaled-sign packet: encoded one at a time, folded or voted from the bits
@@ -964,6 +1087,10 @@ def aggregate_wire(self, payloads, n: Optional[int] = None) -> None:
       validated by ``fc_sign_wire_validate``, uploaded and folded in groups (``fed_avg``,
       ``codec.fold_sign``) or voted over, all resident (``sign_majority``), with ``agg_path =
       "wire-sign"``; the other schemes and a round that mixes the two payload kinds raise.
+      With ``aggregation_config["sign_geometry"] = True`` (default absent) ``krum``, the linear
+      rules and ``pc_analysis: "gram"`` take such a round too: at most ``FC_GRAM_MAX_M`` payloads,
+      all resident, ``codec.gram_sign`` then the "gram" route's consumers, ``agg_path =
+      "wire-sign-gram"``, the bits of ``aggregate_grads``' "sign-gram" route on the same clients.
     Hierarchies, payloads of differing n and a round that does not fit raise
     ``NotImplementedError`` naming the condition."""
     no = _wire_no
@@ -982,7 +1109,8 @@ def aggregate_wire(self, payloads, n: Optional[int] = None) -> None:
         # ---- a round of sign payloads: validated on the host, folded or voted ("wire-sign") ----
         if not all(kinds):
             no("payloads of one kind (the round mixes sign packets and 'top' wire packets)")
-        if type(gar) not in (FedAvg, SignMajority) or gram_wanted(self):
+        geometry = sign_geometry_wanted(self)
+        if (type(gar) not in (FedAvg, SignMajority) or gram_wanted(self)) and not geometry:
             no("fed_avg or sign_majority for sign packets (Krum, the linear rules, the trim rules "
                "and pc_analysis 'gram' have no consumer of sign packets)")
         if cfg.get("devices", DEFAULT_DEVICES) not in (None, 1):
@@ -992,6 +1120,8 @@ def aggregate_wire(self, payloads, n: Optional[int] = None) -> None:
             raise ValueError("SignMajority is unweighted: gradient_weights must be None")
         if w is not None and np.asarray(w).dtype != np.float32:
             no("float32 GAR weights")
+        if geometry and m > L.FC_GRAM_MAX_M:
+            no(f"at most {L.FC_GRAM_MAX_M} payloads for the sign-gram route (got {m})")
         hosts = []
         for i, raw in enumerate(payloads):
             try:
@@ -1004,8 +1134,18 @@ def aggregate_wire(self, payloads, n: Optional[int] = None) -> None:
             if hn != int(n):
                 no(f"payloads of one length n (payload {i} has n = {hn}, not {int(n)})")
             hosts.append((a, h))
-        self.agg_path = "wire-sign"
         self.curr_G = None
+        if geometry:
+            # opt-in ("sign_geometry"): all resident, the Gram family's consumers on the bits
+            total = sum((a.size + 255) & ~255 for a, _ in hosts)
+            b = cfg.get("device_budget_bytes")
+            if b and sign_gram_resident_bytes(int(n), m, total) > int(b):
+                no(f"the round's sign packets to fit device_budget_bytes "
+                   f"({sign_gram_resident_bytes(int(n), m, total)} > {int(b)} bytes)")
+            self.agg_path = "wire-sign-gram"
+            self.agg_grad = sign_wire_gram_round(self, hosts, int(n), _device_of(self)).cpu().numpy()
+            return
+        self.agg_path = "wire-sign"
         self.agg_grad = sign_wire_round(self, hosts, int(n), _device_of(self)).cpu().numpy()
         return
     family = gram_wanted(self)
@@ -1111,7 +1251,7 @@ class Aggregator:
         self.gar = self.__get_gar()
         self.curr_G = None
         self.agg_grad = None
-        self.agg_path = None                # "stream" | "dense-fold" | "dense" | "ef-batch" | "gram" | "sign" | "wire" | "wire-fold" | "wire-sign": the last call's path
+        self.agg_path = None                # "stream" | "dense-fold" | "dense" | "ef-batch" | "gram" | "sign" | "sign-gram" | "wire" | "wire-fold" | "wire-sign" | "wire-sign-gram": the last call's path
         self.agg_draws = None               # streamed np.random draws: "device-mt" | "device-perm" | "host" | None
         self.analyze_pc = self.aggregation_config.get("pc_analysis", False)
         self.num_hierarchies = self.aggregation_config.get("num_hierarchies", 0)

@@ -1468,6 +1468,91 @@ def vote_sign(packets: Sequence[SignPacket], eta: float,
     return out
 
 
+class SignGramWorkspace:
+    """Per-(device, stream) scratch of :func:`gram_sign` (the partial counts; needs no zeroing)."""
+
+    _cache: dict = {}
+    _size = "fc_sign_gram_workspace_bytes"
+
+    def __init__(self, nbytes: int, device: torch.device):
+        self.nbytes = nbytes
+        self.buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+    @classmethod
+    def get(cls, n: int, m: int, device: torch.device):
+        need = int(getattr(L.load(), cls._size)(n, m))
+        key = (device.index if device.index is not None else torch.cuda.current_device(),
+               torch.cuda.current_stream(device).cuda_stream)
+        ws = cls._cache.get(key)
+        if ws is None or ws.nbytes < need:
+            ws = cls(need, device)
+            cls._cache[key] = ws
+        return ws
+
+
+class SignDotWorkspace(SignGramWorkspace):
+    """Per-(device, stream) scratch of :func:`dot_sign` (the partial sums; needs no zeroing)."""
+
+    _cache: dict = {}
+    _size = "fc_sign_dot_workspace_bytes"
+
+
+def _check_sign_round(packets) -> list:
+    pk = _check_sign_packets(packets)
+    if len(pk) > L.FC_GRAM_MAX_M:
+        raise ValueError(f"gram takes at most {L.FC_GRAM_MAX_M} packets (got {len(pk)})")
+    return pk
+
+
+def gram_sign(packets: Sequence[SignPacket], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The (m, m) float64 Gram matrix ``G @ G.T`` of the rows :func:`decode_sign` would make of
+    the packets, computed straight from their bits (fc_sign_gram): ``s_i s_j (n - 2 H_ij)`` with
+    ``H_ij`` the exact Hamming distance, one float64 multiply per entry, so every entry is the
+    correctly rounded inner product and no order of summation exists; a client with a non-finite
+    scale gets a NaN row and column.  At most ``FC_GRAM_MAX_M`` sign packets of one length."""
+    pk = _check_sign_round(packets)
+    m, n, dev = len(pk), pk[0].n, pk[0].words.device
+    if out is None:
+        out = torch.empty((m, m), dtype=torch.float64, device=dev)
+    if (not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or out.device != dev
+            or tuple(out.shape) != (m, m) or not out.is_contiguous() or out.data_ptr() % 16):
+        raise ValueError("out must be a contiguous 16-byte aligned (m, m) float64 tensor on the "
+                         "packets' device")
+    ws = SignGramWorkspace.get(n, m, dev)
+    views = _sign_views(pk, [1.0] * m, dev)
+    L.check(L.load().fc_sign_gram(_vp(views), m, n, _vp(out), _vp(ws.buf), ws.nbytes, _stream(dev)),
+            "fc_sign_gram")
+    return out
+
+
+def dot_sign(packets: Sequence[SignPacket], v: Optional[torch.Tensor] = None,
+             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The (m + 1,) float64 tensor ``[G @ v, v @ v]`` of the rows :func:`decode_sign` would make of
+    the packets (the rows :func:`gram_sign` uses) and a dense float32 device vector ``v``, computed
+    straight from the bits (fc_sign_dot: float64 sums in a fixed order, then one multiply by the
+    scale).  ``v=None`` is the all-ones vector: ``s_i (n - 2 popcount_i)`` exactly, then
+    ``float(n)``.  A client with a non-finite scale gets NaN; a non-finite ``v`` makes every output
+    NaN.  At most ``FC_GRAM_MAX_M`` sign packets of one length."""
+    pk = _check_sign_round(packets)
+    m, n, dev = len(pk), pk[0].n, pk[0].words.device
+    if v is not None:
+        if (not isinstance(v, torch.Tensor) or v.dtype != torch.float32 or v.device != dev
+                or v.numel() != n or not v.is_contiguous() or v.data_ptr() % 16):
+            raise ValueError("v must be a contiguous 16-byte aligned float32 tensor of n elements "
+                             "on the packets' device")
+    if out is None:
+        out = torch.empty(m + 1, dtype=torch.float64, device=dev)
+    if (not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or out.device != dev
+            or tuple(out.shape) != (m + 1,) or not out.is_contiguous() or out.data_ptr() % 16):
+        raise ValueError("out must be a contiguous 16-byte aligned (m + 1,) float64 tensor on the "
+                         "packets' device")
+    ws = SignDotWorkspace.get(n, m, dev)
+    views = _sign_views(pk, [1.0] * m, dev)
+    L.check(L.load().fc_sign_dot(_vp(views), m, n, _vp(v), _vp(out), _vp(ws.buf), ws.nbytes,
+                                 _stream(dev)), "fc_sign_dot")
+    return out
+
+
 def sign_wire_bytes(n: int) -> int:
     """The size of a sign packet's wire form: 128 + 4 fc_sign_words(n)."""
     return L.WIRE_HDR_BYTES + 4 * int(L.load().fc_sign_words(n))

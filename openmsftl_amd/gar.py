@@ -37,7 +37,10 @@ packets (``codec.trimmed_mean``): only a column's non-zeros are ordered, no Gram
 needed, no client is excluded as a whole and the rules take no weights.
 
 ``SignMajority`` is the majority vote over scaled-sign packets (``codec.vote_sign``); ``FedAvg``'s
-``aggregate_packets`` folds such packets with ``codec.fold_sign``.
+``aggregate_packets`` folds such packets with ``codec.fold_sign``.  ``Krum`` and the linear rules
+take a list of such packets too: the Gram matrix is then ``codec.gram_sign`` (exact Hamming
+distances), ``G v`` is ``codec.dot_sign``, Krum's row is ``codec.decode_sign`` and the fold is
+``codec.fold_sign``.
 """
 from __future__ import annotations
 
@@ -47,8 +50,18 @@ import numpy as np
 import torch
 
 from . import codec
+from ._lib import FC_FMT_SIGN
 
 _NP_OF = {torch.float32: np.float32, torch.float64: np.float64}
+
+
+def _sign_round(packets) -> bool:
+    """Is this a round of sign packets?  A list that mixes packet kinds raises ``TypeError``."""
+    kinds = {getattr(p, "fmt", None) == FC_FMT_SIGN for p in packets}
+    if len(kinds) > 1:
+        raise TypeError("a round's packets must be of one kind (sign packets and idx/val packets "
+                        "are mixed)")
+    return kinds == {True}
 
 
 class GAR:
@@ -169,11 +182,14 @@ class Krum(GAR):
 
     def aggregate_packets(self, packets: Sequence["codec.Packet"], out=None,
                           gram: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Krum straight from device packets: Gram (codec.gram, or the one given), selection,
-        then the dense decode of the selected packet."""
+        """Krum straight from device packets: Gram (codec.gram, codec.gram_sign for sign packets,
+        or the one given), selection, then the dense decode of the selected packet."""
+        sign = _sign_round(packets)
         if gram is None:
-            gram = codec.gram(packets)
+            gram = codec.gram_sign(packets) if sign else codec.gram(packets)
         sel = self._pick(gram.cpu().numpy())
+        if sign:
+            return codec.decode_sign(packets[sel], out=out)
         return codec.decode(packets[sel], out=out)
 
     def aggregate(self, G, client_ids=None):
@@ -285,7 +301,8 @@ class LinearRule(GAR):
     the rule's pure coefficient function; stores ``coeffs`` (float64, length M), ``carry`` (0.0
     when no vector is carried) and ``excluded``; then folds ``coeffs.astype(float32)`` over the
     non-excluded packets in row order (``codec.decode_accumulate``), from +0 or from
-    ``torch.mul(v, float32(carry))``.  The aggregate is float32.
+    ``torch.mul(v, float32(carry))``.  The aggregate is float32.  A list of ``codec.SignPacket``
+    takes ``codec.gram_sign``, ``codec.dot_sign`` and ``codec.fold_sign`` instead.
 
     A client whose Gram diagonal is NaN (a non-finite element) is excluded: the rule runs on the
     remaining sub-block, weights restricted (not renormalised), its coefficient is exactly 0
@@ -311,8 +328,9 @@ class LinearRule(GAR):
 
     @staticmethod
     def _dot(packets, keep, v=None):
-        """(b over the kept clients, |v|^2) from codec.dot_dense, both checked to be finite."""
-        r = codec.dot_dense(packets, v).cpu().numpy()
+        """(b over the kept clients, |v|^2) from codec.dot_dense (codec.dot_sign for sign
+        packets), both checked to be finite."""
+        r = (codec.dot_sign if _sign_round(packets) else codec.dot_dense)(packets, v).cpu().numpy()
         b, q = r[:len(packets)][keep], float(r[len(packets)])
         if not (np.all(np.isfinite(b)) and np.isfinite(q)):
             raise ValueError("the carried vector holds a non-finite element (G v is not finite)")
@@ -321,11 +339,13 @@ class LinearRule(GAR):
     def aggregate_packets(self, packets: Sequence["codec.Packet"], out=None,
                           gram: Optional[torch.Tensor] = None) -> torch.Tensor:
         M = len(packets)
+        sign = _sign_round(packets)
+        fold = codec.fold_sign if sign else codec.decode_accumulate
         w = self._weights(M, np.float32)
         if w.dtype != np.float32:
             raise TypeError("aggregate_packets folds with float32 weights")
         if gram is None:
-            gram = codec.gram(packets)
+            gram = codec.gram_sign(packets) if sign else codec.gram(packets)
         K = gram.cpu().numpy()
         bad = np.isnan(np.diagonal(K))
         keep = np.nonzero(~bad)[0]
@@ -340,11 +360,11 @@ class LinearRule(GAR):
         kept = [packets[i] for i in keep]
         weights = [float(c32[i]) for i in keep]
         if v is None:
-            agg = codec.decode_accumulate(kept, weights, out=out)
+            agg = fold(kept, weights, out=out)
         else:
             a32 = float(np.float32(self.carry))
             acc = torch.mul(v, a32) if out is None else torch.mul(v, a32, out=out)
-            agg = codec.decode_accumulate(kept, weights, out=acc, continue_sum=True)
+            agg = fold(kept, weights, out=acc, continue_sum=True)
         self._after(agg)
         return agg
 
@@ -413,9 +433,10 @@ class CenteredClip(LinearRule):
         if v is None:
             a, c = centered_clip_coeffs(K, None, 0.0, self.cclip_tau, self.cclip_iters)
             return c, 0.0, None
-        if v.numel() != n or v.device != packets[0].val.device:
+        dev = packets[0].words.device if _sign_round(packets) else packets[0].val.device
+        if v.numel() != n or v.device != dev:
             raise ValueError(f"the carried vector has {v.numel()} elements on {v.device}; the round has "
-                             f"{n} on {packets[0].val.device} (reset() starts over)")
+                             f"{n} on {dev} (reset() starts over)")
         b, q = self._dot(packets, keep, v)
         a, c = centered_clip_coeffs(K, b, q, self.cclip_tau, self.cclip_iters)
         return c, a, v
