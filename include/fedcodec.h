@@ -633,6 +633,44 @@ int fc_sign_dot(const fc_packet_view* views_dev, int m, uint64_t n,
                 double* out /* DEVICE float64[m + 1], 16-B aligned */,
                 void* ws, size_t ws_bytes, fc_stream_t stream);
 
+/* ---- Coordinate-wise trimmed mean (and median) of scaled-sign packets (fc_sign_trim.hip) ----
+ * What fc_packets_trim gives for idx/val packets, for a round of sign packets: the coordinate-wise
+ * robust rules (Yin, Chen, Ramchandran, Bartlett, ICML 2018) for 1-bit clients, without one decoded
+ * row.  A column holds only the values -+s_i, so np.sort's order of it follows from the order of
+ * the m scales: nothing is sorted per coordinate.
+ * views_dev: DEVICE array of m FC_FMT_SIGN views, exactly as fc_sign_gram takes them: the words in
+ *   `bitmap`, 16-B aligned, with zero bits at and past n and zero pad words; s_i is the float32
+ *   scale in the packet header's p; `weight` is ignored.  1 <= m <= FC_GRAM_MAX_M, 1 <= n < 2^32.
+ * trim: b, the values dropped at each end of a column.  0 <= b, 2 b < m.  b = (m - 1) / 2 is the
+ *   coordinate-wise median (the float32 mean of the two middle values for even m).
+ * out[t], t < n (DEVICE float32[n], 16-B aligned): fc_packets_trim's definition applied to the
+ *   column d_i[t] = b_i[t] ? -s_i : +s_i (the row fc_sign_decode makes): the m values in np.sort's
+ *   order (-0.0 and +0.0 equal, +inf after every finite value, every NaN of either sign after
+ *   +inf); the b smallest and the b largest dropped; the other m - 2b added in ascending order
+ *   from +0.0, every add rounded to float32 (no contraction, no reassociation); the sum divided
+ *   once by float32(m - 2b) in IEEE float32.  A function of the multiset of a column's values
+ *   alone: any order of the clients and any two calls give the same bits.  A client with a NaN
+ *   scale contributes a NaN at the top end of every column and is trimmed like a largest value:
+ *   out[t] is NaN only if more than b scales are NaN (or +inf and -inf both survive).  No client
+ *   is excluded as a whole.  With every scale equal to eta the median is fc_sign_vote(eta) bit for
+ *   bit (2 eta finite), a tie giving +0.0.  The encoder and the validator make s_i >= 0 or NaN;
+ *   a scale with the sign bit set is taken as it stands (the client of |s_i| with every bit
+ *   flipped).
+ * One launch, the grid a function of n alone.  The scales are ranked on the device from the
+ *   headers, once per workgroup (the host reads no header); a lane owns 32 consecutive coordinates
+ *   and walks the clients' bits in rank order, twice; the b steps at each end that cannot land
+ *   in the window [b, m - b) only count or are skipped.  No floating-point atomics, no workgroup
+ *   waits for another (no fc_fused_order_* handling).
+ * Stream-ordered; no allocation, no host synchronisation.  ws: fc_sign_trim_workspace_bytes(n, m)
+ *   bytes, 16-B aligned, NO one-time zeroing; the size is 0 today and ws may then be NULL.
+ * Argument errors return before the GPU is touched: FC_ERR_ARG for a NULL views_dev or out (or
+ *   ws when the size is not 0), m < 1 or m > FC_GRAM_MAX_M, trim < 0, 2 trim >= m, n == 0 (or
+ *   n >= 2^32), an out or ws that is not 16-B aligned; FC_ERR_WORKSPACE for a short workspace. */
+size_t fc_sign_trim_workspace_bytes(uint64_t n, int m);     /* may be 0 */
+int fc_sign_trim(const fc_packet_view* views_dev, int m, uint64_t n, int trim,
+                 float* out /* DEVICE float32[n], 16-B aligned */,
+                 void* ws, size_t ws_bytes, fc_stream_t stream);
+
 /* ---- float64 gradients ------------------------------------------------------------
  * The reference reaches the codec with float64 gradients after RandomGaussian with
  * noise_scale == 0 (attack_models.py:105-106); G takes that dtype (aggregation.py:61) and

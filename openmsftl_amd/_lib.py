@@ -167,6 +167,8 @@ SIGNATURES = {
     "fc_sign_gram": (_i32, [_vp, _i32, _u64, _vp, _vp, _sz, _vp]),
     "fc_sign_dot_workspace_bytes": (_sz, [_u64, _i32]),
     "fc_sign_dot": (_i32, [_vp, _i32, _u64, _vp, _vp, _vp, _sz, _vp]),
+    "fc_sign_trim_workspace_bytes": (_sz, [_u64, _i32]),
+    "fc_sign_trim": (_i32, [_vp, _i32, _u64, _i32, _vp, _vp, _sz, _vp]),
     "fc_topk_dense_f64": (_i32, [_vp, _u64, _u64, _i32, _u64, _u64, _vp, _vp, _sz, _vp]),
     "fc_topk_dense_f64_sampled": (_i32, [_vp, _u64, _u64, _vp, _vp, _sz, _vp, _vp]),
     "fc_mask_dense_f64": (_i32, [_vp, _u64, _i32, _vp, _dbl, _u64, _u64, _vp, _vp]),

@@ -52,6 +52,11 @@ GAR (gar.py:44).  Here the rows never become a dense matrix on the common path:
   same route under the same conditions: one kernel over the resident packets
   (``codec.trimmed_mean``), unweighted (``gradient_weights`` must be None).  The rule needs no
   Gram matrix: it is computed only when ``pc_analysis: "gram"`` asks for the singular values.
+* opt-in (``aggregation_config["sign_trim"] = True``): a round whose clients ALL compress with
+  'sign' under ``trimmed_mean`` / ``coordinate_median`` takes the "sign-trim" route
+  (:func:`sign_trim_route`, :func:`sign_trim_round`): the clients encoded one at a time, all M
+  N/8-byte packets resident, then one kernel over their bits (``codec.trimmed_mean_sign``);
+  ``aggregate_wire`` takes the same clients' payloads as "wire-sign-trim", the same bits.
 
 * ``Aggregator.aggregate_wire(payloads)`` (:func:`aggregate_wire`) aggregates a round from the
   clients' wire packets (``Compression.compress_wire``; include/fedcodec.h) instead of their
@@ -616,13 +621,14 @@ def gram_round(agg, clients, n: int, k: int, dev: torch.device) -> torch.Tensor:
 
 def _gram_family(agg, gar, pk) -> torch.Tensor:
     """The "gram" route's consumers on a round's resident packets (also aggregate_wire's, and
-    the "sign-gram" routes' on sign packets: ``codec.gram_sign`` and ``codec.fold_sign``)."""
+    the "sign-gram" and "sign-trim" routes' on sign packets: ``codec.gram_sign``,
+    ``codec.fold_sign`` and, through the coordinate-wise rules, ``codec.trimmed_mean_sign``)."""
     m = len(pk)
     pc = getattr(agg, "analyze_pc", False) == "gram"
     sign = isinstance(pk[0], codec.SignPacket)
     if isinstance(gar, CoordinateTrim):
         out = gar.aggregate_packets(pk)
-        gram = codec.gram(pk) if pc else None
+        gram = (codec.gram_sign(pk) if sign else codec.gram(pk)) if pc else None
     else:
         gram = codec.gram_sign(pk) if sign else codec.gram(pk)
         if isinstance(gar, (Krum, LinearRule)):
@@ -655,7 +661,9 @@ def sign_route(agg, clients) -> bool:
     outside them raises ``NotImplementedError`` naming the condition, and so does a round of 'sign'
     clients under a scheme that has no consumer of sign packets (Krum, the linear rules, the trim
     rules, ``pc_analysis: "gram"``) unless ``"sign_geometry"`` is set and the scheme is one of
-    :func:`sign_geometry_wanted` (then False: :func:`sign_gram_route` decides).  Touches no GPU (the budget is checked here only when
+    :func:`sign_geometry_wanted` (then False: :func:`sign_gram_route` decides), or ``"sign_trim"``
+    is set and the scheme is a trim rule (:func:`sign_trim_wanted`; then False:
+    :func:`sign_trim_route` decides).  Touches no GPU (the budget is checked here only when
     ``device_budget_bytes`` is configured; :func:`sign_round` checks the default budget)."""
     gar = getattr(agg, "gar", None)
     cfg = getattr(agg, "aggregation_config", None) or {}
@@ -668,6 +676,8 @@ def sign_route(agg, clients) -> bool:
     if gram_wanted(agg):
         if sign_geometry_wanted(agg):
             return False                       # the "sign-gram" route's business (sign_gram_route)
+        if sign_trim_wanted(agg):
+            return False                       # the "sign-trim" route's business (sign_trim_route)
         what = type(gar).__name__ if type(gar) is not FedAvg else "pc_analysis 'gram'"
         raise NotImplementedError(f"{what} has no consumer of sign packets: a round of 'sign' "
                                   "clients takes fed_avg or sign_majority")
@@ -757,7 +767,8 @@ def sign_round(agg, clients, n: int, dev: torch.device) -> torch.Tensor:
 def sign_geometry_wanted(agg) -> bool:
     """Is ``aggregation_config["sign_geometry"]`` set and the scheme one whose geometry sign
     packets can give: Krum, a linear rule, or the device FedAvg with ``pc_analysis: "gram"``?
-    (The coordinate-wise rules have no kernel over sign packets.)"""
+    (The coordinate-wise rules need no geometry: their kernel over sign packets is behind
+    ``"sign_trim"``, :func:`sign_trim_wanted`.)"""
     cfg = getattr(agg, "aggregation_config", None) or {}
     return (bool(cfg.get("sign_geometry", False)) and gram_wanted(agg)
             and not isinstance(agg.gar, CoordinateTrim))
@@ -827,6 +838,14 @@ def sign_gram_round(agg, clients, n: int, dev: torch.device) -> torch.Tensor:
     if need > budget:
         raise NotImplementedError("the sign-gram route (sign_geometry) needs the round's packets to "
                                   f"fit device_budget_bytes ({need} > {budget} bytes)")
+    return _gram_family(agg, agg.gar, _sign_encode_resident(agg, clients, n, dev))
+
+
+def _sign_encode_resident(agg, clients, n: int, dev: torch.device) -> list:
+    """The round's clients uploaded and encoded one at a time into the aggregator's cached sign
+    packets, all M of which stay resident (the "sign-gram" and "sign-trim" routes).  Every
+    residual is checked before one advances; each then advances exactly once."""
+    m = len(clients)
     for c in clients:                          # every residual checked before one advances
         if c.C.error_feedback:
             c.C._ef_buffers(n, dev, allocate=False)
@@ -844,7 +863,7 @@ def sign_gram_round(agg, clients, n: int, dev: torch.device) -> torch.Tensor:
             c.C._ef_commit(res, new, True)
         else:
             codec.encode_sign(g, packet=slot)
-    return _gram_family(agg, agg.gar, pk)
+    return pk
 
 
 def _sign_wire_upload(agg, part, dev: torch.device) -> list:
@@ -867,6 +886,100 @@ def sign_wire_gram_round(agg, hosts, n: int, dev: torch.device) -> torch.Tensor:
     need, budget = sign_gram_resident_bytes(n, len(hosts), total), _budget(agg, dev)
     if need > budget:
         _wire_no(f"the round's sign packets to fit device_budget_bytes ({need} > {budget} bytes)")
+    return _gram_family(agg, agg.gar, _sign_wire_upload(agg, hosts, dev))
+
+
+# ---- the "sign-trim" route (opt-in): the coordinate-wise rules on a round of sign packets ----
+def _sign_trim_no(why: str):
+    raise NotImplementedError(f"the sign-trim route (sign_trim) needs {why}")
+
+
+def sign_trim_wanted(agg) -> bool:
+    """Is ``aggregation_config["sign_trim"]`` set and the scheme a coordinate-wise rule
+    (trimmed_mean, coordinate_median)?  The key does nothing for any other scheme."""
+    cfg = getattr(agg, "aggregation_config", None) or {}
+    return bool(cfg.get("sign_trim", False)) and type(getattr(agg, "gar", None)) in _COORD_RULES
+
+
+def sign_trim_resident_bytes(n: int, m: int, pc: bool = False,
+                             packets_bytes: Optional[int] = None) -> int:
+    """Device bytes the "sign-trim" routes hold at once: the m packets, the aggregate and the
+    gradient in flight (8 n; from payloads, ``packets_bytes`` given, the aggregate alone: 4 n)
+    and the trim kernel's workspace; with ``pc`` (``pc_analysis: "gram"``) the Gram kernel's
+    workspace and the Gram matrix too."""
+    lib = L.load()
+    dense = 8 * n if packets_bytes is None else 4 * n
+    if packets_bytes is None:
+        packets_bytes = m * sign_packet_bytes(n)
+    need = packets_bytes + dense + int(lib.fc_sign_trim_workspace_bytes(n, m))
+    if pc:
+        need += int(lib.fc_sign_gram_workspace_bytes(n, m)) + 8 * m * m
+    return need
+
+
+def _pc_gram(agg) -> bool:
+    return getattr(agg, "analyze_pc", False) == "gram"
+
+
+def sign_trim_route(agg, clients) -> bool:
+    """Does this round take the "sign-trim" route?  False without the key, under a scheme that is
+    no coordinate-wise rule, or when not every client compresses with 'sign' (the other routes
+    decide).  Otherwise the conditions of :func:`sign_gram_route`: each failure is a
+    ``NotImplementedError`` naming the condition, and a ``gradient_weights`` that is not None is
+    the rules' ``ValueError``.  Touches no GPU."""
+    if not sign_trim_wanted(agg):
+        return False
+    if not all(getattr(c.C, "compression_function", None) == "sign" for c in clients):
+        return False
+    no = _sign_trim_no
+    cfg = getattr(agg, "aggregation_config", None) or {}
+    if not all(isinstance(c.C, Compression) for c in clients):
+        no("every client to be the drop-in Compression")
+    if agg.num_hierarchies != 0:
+        no("no hierarchies (num_hierarchies == 0)")
+    if cfg.get("devices", DEFAULT_DEVICES) not in (None, 1):
+        no("one device")
+    if getattr(agg.gar, "gradient_weights", None) is not None:
+        raise ValueError(f"{type(agg.gar).__name__} is unweighted: gradient_weights must be None")
+    n = None
+    for c in clients:
+        g = np.asarray(c.grad)
+        if g.ndim != 1 or g.dtype != np.float32:
+            no("1-D float32 gradients")
+        if n is not None and g.shape[0] != n:
+            no("gradients of one length")
+        n = g.shape[0]
+    if n == 0:
+        no("a gradient length n > 0")
+    m = len(clients)
+    if m > L.FC_GRAM_MAX_M:
+        no(f"at most {L.FC_GRAM_MAX_M} clients (got {m})")
+    b = cfg.get("device_budget_bytes")
+    need = sign_trim_resident_bytes(n, m, _pc_gram(agg))
+    if b and need > int(b):
+        no(f"the round's packets to fit device_budget_bytes ({need} > {int(b)} bytes)")
+    return True
+
+
+def sign_trim_round(agg, clients, n: int, dev: torch.device) -> torch.Tensor:
+    """One round on the "sign-trim" route: the clients are uploaded and encoded one at a time as
+    in :func:`sign_gram_round` (with error feedback each residual advances exactly once), all M
+    packets stay resident, then :func:`_gram_family` runs the rule on them
+    (``codec.trimmed_mean_sign``; ``codec.gram_sign`` only for ``pc_analysis: "gram"``)."""
+    need, budget = sign_trim_resident_bytes(n, len(clients), _pc_gram(agg)), _budget(agg, dev)
+    if need > budget:
+        _sign_trim_no(f"the round's packets to fit device_budget_bytes ({need} > {budget} bytes)")
+    return _gram_family(agg, agg.gar, _sign_encode_resident(agg, clients, n, dev))
+
+
+def sign_wire_trim_round(agg, hosts, n: int, dev: torch.device) -> torch.Tensor:
+    """aggregate_wire's round of validated sign payloads under ``sign_trim``: all uploaded into
+    the cached slab, then :func:`_gram_family` (the bits of :func:`sign_trim_round`)."""
+    total = sum((a.size + 255) & ~255 for a, _ in hosts)
+    need = sign_trim_resident_bytes(n, len(hosts), _pc_gram(agg), total)
+    budget = _budget(agg, dev)
+    if need > budget:
+        _sign_trim_no(f"the round's sign packets to fit device_budget_bytes ({need} > {budget} bytes)")
     return _gram_family(agg, agg.gar, _sign_wire_upload(agg, hosts, dev))
 
 
@@ -915,7 +1028,10 @@ def aggregate_grads(self, clients: List, input_feature: np.ndarray = None,
     sign = sign_route(self, clients)
     # opt-in ("sign_geometry"): the Gram family's consumers on a round of sign packets
     sign_gram = sign_gram_route(self, clients)
-    k_gram = gram_route_k(self, clients) if gram_wanted(self) and not sign_gram else None
+    # opt-in ("sign_trim"): the coordinate-wise rules on a round of sign packets
+    sign_trim = sign_trim_route(self, clients)
+    k_gram = (gram_route_k(self, clients)
+              if gram_wanted(self) and not sign_gram and not sign_trim else None)
     dev = _device_of(self)
     grad0 = np.asarray(clients[0].grad)
     n = grad0.shape[0]
@@ -932,6 +1048,12 @@ def aggregate_grads(self, clients: List, input_feature: np.ndarray = None,
         self.agg_path = "sign-gram"
         self.curr_G = None
         self.agg_grad = sign_gram_round(self, clients, n, dev).cpu().numpy()
+        return
+    if sign_trim:
+        # every client a scaled-sign packet, all resident: the trimmed mean straight from the bits
+        self.agg_path = "sign-trim"
+        self.curr_G = None
+        self.agg_grad = sign_trim_round(self, clients, n, dev).cpu().numpy()
         return
     if sign:
         # every client a scaled-sign packet: encoded one at a time, folded or voted from the bits
@@ -1091,6 +1213,10 @@ def aggregate_wire(self, payloads, n: Optional[int] = None) -> None:
       rules and ``pc_analysis: "gram"`` take such a round too: at most ``FC_GRAM_MAX_M`` payloads,
       all resident, ``codec.gram_sign`` then the "gram" route's consumers, ``agg_path =
       "wire-sign-gram"``, the bits of ``aggregate_grads``' "sign-gram" route on the same clients.
+      With ``aggregation_config["sign_trim"] = True`` (default absent) ``trimmed_mean`` and
+      ``coordinate_median`` take such a round: at most ``FC_GRAM_MAX_M`` payloads, all resident,
+      ``codec.trimmed_mean_sign``, ``agg_path = "wire-sign-trim"``, the bits of
+      ``aggregate_grads``' "sign-trim" route on the same clients.
     Hierarchies, payloads of differing n and a round that does not fit raise
     ``NotImplementedError`` naming the condition."""
     no = _wire_no
@@ -1110,7 +1236,8 @@ def aggregate_wire(self, payloads, n: Optional[int] = None) -> None:
         if not all(kinds):
             no("payloads of one kind (the round mixes sign packets and 'top' wire packets)")
         geometry = sign_geometry_wanted(self)
-        if (type(gar) not in (FedAvg, SignMajority) or gram_wanted(self)) and not geometry:
+        trim = sign_trim_wanted(self)
+        if (type(gar) not in (FedAvg, SignMajority) or gram_wanted(self)) and not geometry and not trim:
             no("fed_avg or sign_majority for sign packets (Krum, the linear rules, the trim rules "
                "and pc_analysis 'gram' have no consumer of sign packets)")
         if cfg.get("devices", DEFAULT_DEVICES) not in (None, 1):
@@ -1118,10 +1245,14 @@ def aggregate_wire(self, payloads, n: Optional[int] = None) -> None:
         w = getattr(gar, "gradient_weights", None)
         if w is not None and type(gar) is SignMajority:
             raise ValueError("SignMajority is unweighted: gradient_weights must be None")
+        if w is not None and trim:
+            raise ValueError(f"{type(gar).__name__} is unweighted: gradient_weights must be None")
         if w is not None and np.asarray(w).dtype != np.float32:
             no("float32 GAR weights")
         if geometry and m > L.FC_GRAM_MAX_M:
             no(f"at most {L.FC_GRAM_MAX_M} payloads for the sign-gram route (got {m})")
+        if trim and m > L.FC_GRAM_MAX_M:
+            _sign_trim_no(f"at most {L.FC_GRAM_MAX_M} payloads (got {m})")
         hosts = []
         for i, raw in enumerate(payloads):
             try:
@@ -1144,6 +1275,17 @@ def aggregate_wire(self, payloads, n: Optional[int] = None) -> None:
                    f"({sign_gram_resident_bytes(int(n), m, total)} > {int(b)} bytes)")
             self.agg_path = "wire-sign-gram"
             self.agg_grad = sign_wire_gram_round(self, hosts, int(n), _device_of(self)).cpu().numpy()
+            return
+        if trim:
+            # opt-in ("sign_trim"): all resident, the trimmed mean straight from the bits
+            total = sum((a.size + 255) & ~255 for a, _ in hosts)
+            b = cfg.get("device_budget_bytes")
+            need = sign_trim_resident_bytes(int(n), m, _pc_gram(self), total)
+            if b and need > int(b):
+                _sign_trim_no(f"the round's sign packets to fit device_budget_bytes ({need} > "
+                              f"{int(b)} bytes)")
+            self.agg_path = "wire-sign-trim"
+            self.agg_grad = sign_wire_trim_round(self, hosts, int(n), _device_of(self)).cpu().numpy()
             return
         self.agg_path = "wire-sign"
         self.agg_grad = sign_wire_round(self, hosts, int(n), _device_of(self)).cpu().numpy()
@@ -1251,7 +1393,7 @@ class Aggregator:
         self.gar = self.__get_gar()
         self.curr_G = None
         self.agg_grad = None
-        self.agg_path = None                # "stream" | "dense-fold" | "dense" | "ef-batch" | "gram" | "sign" | "sign-gram" | "wire" | "wire-fold" | "wire-sign" | "wire-sign-gram": the last call's path
+        self.agg_path = None                # "stream" | "dense-fold" | "dense" | "ef-batch" | "gram" | "sign" | "sign-gram" | "sign-trim" | "wire" | "wire-fold" | "wire-sign" | "wire-sign-gram" | "wire-sign-trim": the last call's path
         self.agg_draws = None               # streamed np.random draws: "device-mt" | "device-perm" | "host" | None
         self.analyze_pc = self.aggregation_config.get("pc_analysis", False)
         self.num_hierarchies = self.aggregation_config.get("num_hierarchies", 0)

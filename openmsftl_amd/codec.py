@@ -1553,6 +1553,40 @@ def dot_sign(packets: Sequence[SignPacket], v: Optional[torch.Tensor] = None,
     return out
 
 
+class SignTrimWorkspace(SignGramWorkspace):
+    """Per-(device, stream) scratch of :func:`trimmed_mean_sign`, taken only when
+    ``fc_sign_trim_workspace_bytes`` is not 0 (needs no zeroing)."""
+
+    _cache: dict = {}
+    _size = "fc_sign_trim_workspace_bytes"
+
+
+def trimmed_mean_sign(packets: Sequence[SignPacket], trim: int,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The (n,) float32 coordinate-wise trimmed mean of the rows :func:`decode_sign` would make of
+    the packets, computed straight from their bits (fc_sign_trim): :func:`trimmed_mean`'s
+    definition on columns that hold only ``-s_i`` and ``+s_i``, whose ``np.sort`` order follows
+    from the order of the scales, so nothing is sorted per coordinate.  ``trim = (m - 1) // 2`` is
+    the coordinate-wise median.  A client with a NaN scale is trimmed like a largest value in every
+    column.  At most ``FC_GRAM_MAX_M`` sign packets of one length; ``0 <= trim`` and
+    ``2 * trim < m``."""
+    pk = _check_sign_round(packets)
+    m, n, dev = len(pk), pk[0].n, pk[0].words.device
+    trim = _check_trim(m, trim)
+    lib = L.load()
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=dev)
+    if (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != dev
+            or tuple(out.shape) != (n,) or not out.is_contiguous() or out.data_ptr() % 16):
+        raise ValueError("out must be a contiguous 16-byte aligned (n,) float32 tensor on the "
+                         "packets' device")
+    ws = SignTrimWorkspace.get(n, m, dev) if int(lib.fc_sign_trim_workspace_bytes(n, m)) else None
+    views = _sign_views(pk, [1.0] * m, dev)
+    L.check(lib.fc_sign_trim(_vp(views), m, n, trim, _vp(out), _vp(ws.buf if ws else None),
+                             ws.nbytes if ws else 0, _stream(dev)), "fc_sign_trim")
+    return out
+
+
 def sign_wire_bytes(n: int) -> int:
     """The size of a sign packet's wire form: 128 + 4 fc_sign_words(n)."""
     return L.WIRE_HDR_BYTES + 4 * int(L.load().fc_sign_words(n))

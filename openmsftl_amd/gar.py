@@ -40,7 +40,9 @@ needed, no client is excluded as a whole and the rules take no weights.
 ``aggregate_packets`` folds such packets with ``codec.fold_sign``.  ``Krum`` and the linear rules
 take a list of such packets too: the Gram matrix is then ``codec.gram_sign`` (exact Hamming
 distances), ``G v`` is ``codec.dot_sign``, Krum's row is ``codec.decode_sign`` and the fold is
-``codec.fold_sign``.
+``codec.fold_sign``.  The coordinate-wise rules take them as well (``codec.trimmed_mean_sign``): a
+column of such packets holds only ``-s_i`` and ``+s_i``, so its order follows from the order of
+the scales and nothing is sorted per coordinate.
 """
 from __future__ import annotations
 
@@ -451,7 +453,8 @@ class CoordinateTrim(GAR):
     clients' values are ordered as ``np.sort`` does, the ``trim`` smallest and largest dropped and
     the float32 mean of the rest taken (``codec.trimmed_mean``: ascending float32 sum from +0.0,
     then one division).  ``aggregate_packets`` reads the packets alone: no dense G and no Gram
-    matrix.  ``trim`` holds the count used in the last round.
+    matrix; a list of ``codec.SignPacket`` takes ``codec.trimmed_mean_sign`` instead (a list that
+    mixes the two kinds raises ``TypeError``).  ``trim`` holds the count used in the last round.
 
     The rules are unweighted and exclude no client as a whole: a ``gradient_weights`` that is not
     None raises (a DGA weight vector silently ignored would be a wrong result), and a client with
@@ -473,7 +476,10 @@ class CoordinateTrim(GAR):
     def aggregate_packets(self, packets: Sequence["codec.Packet"], out=None) -> torch.Tensor:
         if self.gradient_weights is not None:
             raise ValueError(f"{type(self).__name__} is unweighted: gradient_weights must be None")
+        sign = _sign_round(packets)
         self.trim = self._trim_of(len(packets))
+        if sign:
+            return codec.trimmed_mean_sign(packets, self.trim, out=out)
         return codec.trimmed_mean(packets, self.trim, out=out)
 
 
