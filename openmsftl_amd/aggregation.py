@@ -3,78 +3,85 @@
 The reference builds the dense host matrix ``G`` (M x N) row by row from
 ``client.C.compress(client.grad)`` (aggregation.py:61-63), optionally merges client clusters
 (``__merge_gradient``, aggregation.py:80-93, ``num_hierarchies > 0``) and reduces it with the
-GAR (gar.py:44).  Here the rows never become a dense matrix on the common path:
+GAR (gar.py:44).  Here a round takes one route, named by ``agg_path`` afterwards; on all but
+"dense" the rows never become a dense matrix.  Every result is bit-exact against the reference
+(tests/golden/make_golden_agg.py pins the merge and the sign-of-zero semantics;
+tests/test_gpu_parity.py runs both paths), and routes that share clients give the same bits.
 
-* when every client's codec is one of compression.py's ('full', 'top', 'rand',
-  'dropout-biased', 'dropout-unbiased') on float32 gradients, their host gradients stream
-  through a bounded device ring (openmsftl_amd/pipeline.py): H2D, each row made on the device
-  (top-k packets, mask packets whose masks are drawn on the host from the global
-  ``np.random`` in row order exactly as the reference draws them, or the dense gradient for
-  'full'), and every group folded into the FedAVG sum in row order (``fc_decode_accumulate``
-  / ``fc_weighted_sum_dense_continue``: bit-exact ``np.sum(G * w[:, None], axis=0)``).  G is
-  never built and device memory stays within ``device_budget_bytes`` for any client count.
-  ``aggregation_config["devices"]`` (or ``integration.install(devices=...)``) fans the groups
-  out round-robin over several GPUs, one pipeline and host thread each, the running sum
-  hopping between them in group order; the default is the current device only;
-* with hierarchies each first-stage cluster mean is the streamed fold with weights 1 (the
-  +0-started row-order sum ``np.mean`` computes) divided once by the row count
-  (``fc_div_scalar``); later stages do the same over the dense merged rows
-  (``fc_weighted_sum_dense``); the GAR then reduces the merged rows.
-* 'qsgd' (opt-in) or a codec the reference rejects, float64 gradients (``RandomGaussian``
-  with ``noise_scale == 0``, attack_models.py:105-106) and float64 GAR weights take the
-  generic path: the drop-in ``Compression`` per client in row order on the device (same NumPy
-  RNG draws as the reference, the same exceptions at the same row), each row cast to G's dtype
-  and folded at once into the GAR's sum in NumPy's promoted dtype (``fold_rows``: one row of
-  device memory); only a merge (hierarchies) or a host GAR stacks the rows into G.
-* opt-in (``aggregation_config["batched_error_feedback"]``): a round whose clients ALL compress
-  with 'top' and error feedback takes the "ef-batch" route (:func:`ef_batch_k`,
-  :func:`ef_batch_fold`): groups of <= 64 clients encoded by one fc_topk_encode_ef_batch launch
-  chain and folded in row order, the same bits as the generic path.
+``aggregate_grads(clients)``: :func:`round_route` decides on the host, before a GPU is touched, in
+the order of the first five rows; the rest is the tail of ``aggregate_grads``.
+``aggregate_wire(payloads)`` takes the clients' wire packets (``Compression.compress_wire``;
+include/fedcodec.h) instead, validated on the host: the "wire*" rows, each the bits of the row it
+names on the same clients.  A round that a scheme or a key claims but whose conditions fail raises
+``NotImplementedError`` naming the condition (no silent dense fallback).  "Packet round" below: no
+hierarchies, one device, float32 or no GAR weights, 1-D float32 gradients (payloads) of one length.
 
-* ``aggregation_scheme: "krum"`` (gar.Krum) and ``aggregation_config["pc_analysis"] = "gram"``
-  take the "gram" route (:func:`gram_route_k`, :func:`gram_round`): the whole round's 'top'
-  packets resident at once (upload, one batched encode, resolve), their M x M float64 Gram matrix
-  straight from the packets (``codec.gram``), then the FedAVG fold (the "stream" route's bits:
-  the same encode, the same row-order fold) or Krum's selection.  With ``pc_analysis: "gram"``
-  the singular values of G, ``sqrt(max(eigvalsh(gram), 0))`` descending (float64, length M,
-  all NaN when the Gram holds NaN), are appended to ``self.gar.Sigma_tracked`` after the
-  round.  Unlike the reference's ``randomized_svd`` this draws nothing from ``np.random``, so
-  the global RNG stream of a run differs from the reference's by exactly those draws.  The
-  string is deliberate: ``pc_analysis: True`` keeps raising on the device class as before.  A
-  round that does not meet the route's conditions raises ``NotImplementedError`` naming the
-  condition (no silent dense fallback).
-* ``aggregation_scheme: "spectral_gram"`` / ``"geometric_median"`` / ``"centered_clip"``
-  (gar.LinearRule) take the same route: coefficients from the Gram matrix (and
-  ``codec.dot_dense`` for row sums or a carried vector), then the row-order fold of the packets
-  with those coefficients.  ``"fed_spectral_avg"`` (the reference's class, with its autoencoder
-  branch) keeps raising.
-* ``aggregation_scheme: "trimmed_mean"`` / ``"coordinate_median"`` (gar.CoordinateTrim) take the
-  same route under the same conditions: one kernel over the resident packets
-  (``codec.trimmed_mean``), unweighted (``gradient_weights`` must be None).  The rule needs no
-  Gram matrix: it is computed only when ``pc_analysis: "gram"`` asks for the singular values.
-* opt-in (``aggregation_config["sign_trim"] = True``): a round whose clients ALL compress with
-  'sign' under ``trimmed_mean`` / ``coordinate_median`` takes the "sign-trim" route
-  (:func:`sign_trim_route`, :func:`sign_trim_round`): the clients encoded one at a time, all M
-  N/8-byte packets resident, then one kernel over their bits (``codec.trimmed_mean_sign``);
-  ``aggregate_wire`` takes the same clients' payloads as "wire-sign-trim", the same bits.
+================  ================================================  ====================  ====================================
+``agg_path``      conditions                                        opt-in key            resident on the device
+================  ================================================  ====================  ====================================
+"sign-gram"       packet round, n > 0, all clients the drop-in      ``sign_geometry``     M sign packets (N/8 bytes each),
+                  'sign', M <= 128; krum, spectral_gram,                                  Gram and dot workspaces, 8 M^2
+                  geometric_median, centered_clip or fed_avg with                         (:func:`sign_gram_resident_bytes`)
+                  ``pc_analysis: "gram"``
+"sign-trim"       the same clients; trimmed_mean or                 ``sign_trim``         M sign packets, trim workspace
+                  coordinate_median, unweighted                                           (:func:`sign_trim_resident_bytes`)
+"gram"            packet round, all clients 'top' without error     the scheme (krum,     M gradients and their 'top' packets,
+                  feedback at one fraction with 0 < k < n,          the linear and trim   encode, Gram, dot (and trim)
+                  M <= 128 (:func:`gram_wanted`,                    rules), or            workspaces, 8 M^2
+                  :func:`gram_route_k`)                             ``pc_analysis:        (:func:`gram_resident_bytes`)
+                                                                    "gram"``
+"sign"            the "sign-gram" clients; fed_avg (a round         on; off with          fed_avg: a group of sign packets
+                  outside the conditions goes on down this          ``sign_packets:       sized by the budget;
+                  table) or sign_majority (it is refused,           False`` (fed_avg)     sign_majority: all M
+                  unweighted) (:func:`sign_route`)
+"ef-batch"        packet round, fed_avg, all clients the drop-in    ``batched_error_      groups of <= 64 gradients, residuals
+                  'top' with error feedback at one fraction with    feedback``            and packets (:func:`ef_batch_group`)
+                  0 < k < n (:func:`ef_batch_k`)
+"stream"          a device GAR, float32 gradients and weights,      -                     a bounded ring of gradients and a
+                  n > 0, every codec 'full', 'top', 'rand' or                             group of packets per device
+                  'dropout-*' without state (:func:`row_plan`);                           (``devices``), within
+                  with hierarchies the merged rows go to the GAR                          ``device_budget_bytes``
+"dense-fold"      anything else under a device GAR without          -                     one row (:func:`fold_rows`)
+                  hierarchies: 'qsgd', error feedback, float64
+                  gradients or weights, a codec the reference
+                  rejects (it raises at the same row)
+"dense"           anything else: hierarchies over such rows, or a   -                     G (M x N)
+                  reference GAR (:func:`integration.install`)
+"wire"            packet round of 'top' payloads; fed_avg           -                     a group's wire bytes and slotted
+                  ("stream"), any M in groups, or a scheme of                             packets; the "gram" schemes: all M
+                  "gram", M <= 128                                                        (:func:`wire_resident_bytes`)
+"wire-fold"       the same under fed_avg, no slotted packets        ``wire_fold``         a group's wire bytes
+                                                                                          (:func:`wire_fold_groups`)
+"wire-sign"       packet round of sign payloads; fed_avg in         -                     a group's sign packets;
+                  groups or sign_majority ("sign")                                        sign_majority: all M
+"wire-sign-gram"  the same, M <= 128, the schemes of "sign-gram"    ``sign_geometry``     as "sign-gram"
+"wire-sign-trim"  the same, M <= 128, the schemes of "sign-trim"    ``sign_trim``         as "sign-trim"
+================  ================================================  ====================  ====================================
 
-* ``Aggregator.aggregate_wire(payloads)`` (:func:`aggregate_wire`) aggregates a round from the
-  clients' wire packets (``Compression.compress_wire``; include/fedcodec.h) instead of their
-  gradients: validated on the host, uploaded, unpacked into slotted packets, then the fold of
-  the "stream" route or the Gram family's ``aggregate_packets``: the same bits, ``agg_path =
-  "wire"``.  ``aggregation_config["wire_fold"] = True`` (default off) folds FedAvg straight from
-  the uploaded wire bytes instead (``codec.fold_wire``, no slotted packets): the same bits,
-  ``agg_path = "wire-fold"``.
+* "stream": the host gradients go through the ring (openmsftl_amd/pipeline.py): H2D, each row made
+  on the device (top-k packets, mask packets whose masks are np.random's own draws in row order,
+  made on the host or, :data:`DEVICE_MT` / :data:`DEVICE_PERM`, on the device, or the dense
+  gradient), every group folded in row order (bit-exact ``np.sum(G * w[:, None], axis=0)``).
+  ``aggregation_config["devices"]`` fans the groups out round-robin over several GPUs, the running
+  sum hopping between them in group order.  With hierarchies each first-stage cluster mean is the
+  streamed fold with weights 1 divided once by the row count; later stages do the same over the
+  dense merged rows (:func:`merge_streamed`, :func:`merge_stages`).
+* "gram", "sign-gram", "sign-trim" and their wire rows: all of the round's packets resident, then
+  :func:`_gram_family`: the M x M float64 Gram matrix straight from the packets
+  (``codec.gram`` / ``codec.gram_sign``) and Krum's selection, a linear rule's coefficients and
+  fold, or the FedAVG fold ("stream"'s bits); a trim rule runs one kernel over the packets
+  (``codec.trimmed_mean`` / ``codec.trimmed_mean_sign``) and needs no Gram matrix.  With
+  ``pc_analysis: "gram"`` the singular values of G, ``sqrt(max(eigvalsh(gram), 0))`` descending,
+  are appended to ``gar.Sigma_tracked``; unlike the reference's ``randomized_svd`` this draws
+  nothing from ``np.random``.  ``pc_analysis: True`` and ``"fed_spectral_avg"`` keep raising.
 
 ``aggregate_grads`` is a plain function so that :func:`openmsftl_amd.integration.install` can
 bind it onto the REFERENCE ``Aggregator`` class (its ``self.gar`` may then be a reference GAR
 with no ``aggregate_packets``: G is then handed over as the host array the reference builds).
-
-Results are bit-exact against the reference (tests/golden/make_golden_agg.py pins the merge and
-the sign-of-zero semantics; tests/test_gpu_parity.py runs both paths).  Out of the hot path and
-not rebuilt: ``pc_analysis`` (randomized SVD of G), ``SpectralFedAvg``, ``update_model`` and the
-RL / DGA aggregators: the device class raises ``NotImplementedError`` for them,
-the patched reference class keeps its own code for ``pc_analysis``.
+Out of the hot path and not rebuilt: ``pc_analysis`` (randomized SVD of G), ``SpectralFedAvg``,
+``update_model`` and the RL / DGA aggregators: the device class raises
+``NotImplementedError`` for them, the patched reference class keeps its own code for
+``pc_analysis``.
 """
 from __future__ import annotations
 
@@ -128,8 +135,7 @@ def stream_devices(agg) -> List[torch.device]:
     list of device indices (repeats allowed: tests stand two pipelines on one GPU in for two
     GPUs); absent -> :data:`DEFAULT_DEVICES` (None: the current device).  An aggregator
     constructed with an explicit ``device`` and no ``devices`` key stays on that device."""
-    cfg = getattr(agg, "aggregation_config", None) or {}
-    spec = cfg.get("devices")
+    spec = _config(agg).get("devices")
     if spec is None:
         if isinstance(getattr(agg, "device", None), torch.device):
             return [_device_of(agg)]
@@ -430,6 +436,156 @@ def fold_rows(gar, clients, n: int, tdt: torch.dtype, dev: torch.device) -> torc
     return acc
 
 
+# ---- the round conditions, each written once ---------------------------------------------------
+# Every check takes ``no``, the function that refuses: a route's own ``_needs(prefix)`` (a
+# ``NotImplementedError`` naming the route and the condition), or ``_refused`` where the caller
+# answers None / False instead (ef_batch_k, sign_route under fed_avg).
+class _Refused(Exception):
+    """A round condition that does not hold: only the ``why`` text."""
+
+
+def _refused(why: str):
+    raise _Refused(why)
+
+
+def _needs(prefix: str):
+    def no(why: str):
+        raise NotImplementedError(f"{prefix} needs {why}")
+    return no
+
+
+_gram_no = _needs("the gram route (krum / pc_analysis='gram')")
+_sign_no = _needs("the sign route (sign packets: fed_avg / sign_majority)")
+_sign_gram_no = _needs("the sign-gram route (sign_geometry)")
+_sign_trim_no = _needs("the sign-trim route (sign_trim)")
+_wire_no = _needs("aggregate_wire")
+
+
+def _config(agg) -> dict:
+    return getattr(agg, "aggregation_config", None) or {}
+
+
+def _no_hierarchies(agg, no) -> None:
+    if agg.num_hierarchies != 0:
+        no("no hierarchies (num_hierarchies == 0)")
+
+
+def _one_device(agg, no) -> None:
+    if _config(agg).get("devices", DEFAULT_DEVICES) not in (None, 1):
+        no("one device")
+
+
+def _f32_weights(gar, no) -> None:
+    w = getattr(gar, "gradient_weights", None)
+    if w is not None and np.asarray(w).dtype != np.float32:
+        no("float32 GAR weights")
+
+
+def _drop_in(clients, no) -> None:
+    if not all(isinstance(c.C, Compression) for c in clients):
+        no("every client to be the drop-in Compression")
+
+
+def _grad_length(c, n: Optional[int], no) -> int:
+    """This client's gradient length; ``n`` is the length of the clients before it."""
+    g = np.asarray(c.grad)
+    if g.ndim != 1 or g.dtype != np.float32:
+        no("1-D float32 gradients")
+    if n is not None and g.shape[0] != n:
+        no("gradients of one length")
+    return g.shape[0]
+
+
+def _at_most(m: int, what: str, no) -> None:
+    if m > L.FC_GRAM_MAX_M:
+        no(f"at most {L.FC_GRAM_MAX_M} {what} (got {m})")
+
+
+def _top_round(clients, error_feedback: bool, no):
+    """(n, k) of a round whose clients all compress with 'top', error feedback on for all or for
+    none, at one finite fraction with 0 < k < n, on 1-D float32 gradients of one length."""
+    n, fr = None, None
+    for c in clients:
+        C = c.C
+        if getattr(C, "compression_function", None) != "top":
+            no("every client to compress with 'top'")
+        if bool(getattr(C, "error_feedback", False)) != error_feedback:
+            no("'top' with error feedback" if error_feedback else "'top' without error feedback")
+        n = _grad_length(c, n, no)
+        f = C.fraction_coordinates
+        if not isinstance(f, (int, float, np.floating, np.integer)) or not np.isfinite(f):
+            no("a finite fraction_coordinates")
+        if fr is not None and f != fr:
+            no("one common fraction_coordinates")
+        fr = f
+    k = kept_count(fr, n)
+    if not 0 < k < n:
+        no(f"0 < k < n (k={k}, n={n})")
+    return n, k
+
+
+def _all_sign(clients) -> bool:
+    return all(getattr(c.C, "compression_function", None) == "sign" for c in clients)
+
+
+def _sign_conditions(agg, clients, no, unweighted: bool = False) -> int:
+    """n of a round of 'sign' clients that may stay on the device as packets: every client the
+    drop-in ``Compression``, no hierarchies, one device, float32 or no weights (``unweighted``: the
+    rule's ``ValueError`` for any), 1-D float32 gradients of one length n > 0."""
+    _drop_in(clients, no)
+    _no_hierarchies(agg, no)
+    _one_device(agg, no)
+    if unweighted:
+        agg.gar._unweighted()
+    else:
+        _f32_weights(agg.gar, no)
+    n = None
+    for c in clients:
+        n = _grad_length(c, n, no)
+    if n == 0:
+        no("a gradient length n > 0")
+    return n
+
+
+def _fit(agg, need: int, no, dev: Optional[torch.device] = None, what: str = "packets",
+         tail: str = "") -> None:
+    """The budget check.  Without ``dev`` (on the host, no GPU touched) only a configured
+    ``device_budget_bytes`` is compared; with it :func:`_budget`, whose default reads the free
+    memory."""
+    configured = _config(agg).get("device_budget_bytes")
+    if dev is None and not configured:
+        return
+    limit = int(configured) if dev is None else _budget(agg, dev)
+    if need > limit:
+        no(f"the round's {what} to fit device_budget_bytes ({need} > {limit} bytes){tail}")
+
+
+def _cached(agg, attr: str, key, count: int, make) -> list:
+    """``count`` packets from the list ``make(count)`` made, kept at ``agg.<attr>[key]``: made
+    again when absent or too short, the lists of other keys released first (one shape at a time;
+    a ``"slab"`` stays)."""
+    cache = agg.__dict__.setdefault(attr, {})
+    packets = cache.get(key)
+    if packets is None or len(packets) < count:
+        for other in [k for k in cache if k != "slab"]:
+            del cache[other]
+        packets = cache[key] = make(count)
+    return packets[:count]
+
+
+def _slab_upload(agg, attr: str, upload, part, dev: torch.device) -> list:
+    """Validated payloads (``(bytes, header)`` pairs) into the device slab cached at
+    ``agg.<attr>["slab"]``, 256-byte aligned each, by ``upload`` (``codec._wire_upload`` /
+    ``codec._sign_upload``): the packets are views of it."""
+    cache = agg.__dict__.setdefault(attr, {})
+    offs = np.concatenate([[0], np.cumsum([codec.slab_bytes(a.size) for a, _ in part])])
+    slab = cache.get("slab")
+    if slab is None or slab.device != dev or slab.numel() < int(offs[-1]):
+        cache.pop("slab", None)
+        slab = cache["slab"] = torch.empty(int(offs[-1]), dtype=torch.uint8, device=dev)
+    return [upload(a, h, dev, out=slab[int(o): int(o) + a.size]) for (a, h), o in zip(part, offs)]
+
+
 #: clients per batched error-feedback encode at most (k_compact_mag1's interleave group)
 EF_BATCH_GROUP = 64
 
@@ -440,31 +596,18 @@ def ef_batch_k(agg, clients) -> Optional[int]:
     float32 (or no) weights, no hierarchies, one device, and EVERY client is the drop-in
     Compression with 'top', error feedback on and one common fraction with 0 < k < n, on 1-D
     float32 gradients of one length.  Touches no GPU."""
-    cfg = getattr(agg, "aggregation_config", None) or {}
-    if not cfg.get("batched_error_feedback", False) or not clients:
+    if not _config(agg).get("batched_error_feedback", False) or not clients:
         return None
-    if type(agg.gar) is not FedAvg or agg.num_hierarchies != 0:
+    if type(agg.gar) is not FedAvg:
         return None
-    if cfg.get("devices", DEFAULT_DEVICES) not in (None, 1):      # multi-GPU rounds: dense-fold
+    try:
+        _no_hierarchies(agg, _refused)
+        _one_device(agg, _refused)                                # multi-GPU rounds: dense-fold
+        _f32_weights(agg.gar, _refused)
+        _drop_in(clients, _refused)
+        return _top_round(clients, True, _refused)[1]
+    except _Refused:
         return None
-    w = getattr(agg.gar, "gradient_weights", None)
-    if w is not None and np.asarray(w).dtype != np.float32:
-        return None
-    n, fr = None, None
-    for c in clients:
-        C, g = c.C, np.asarray(c.grad)
-        if not isinstance(C, Compression) or C.compression_function != "top" or not C.error_feedback:
-            return None
-        if g.ndim != 1 or g.dtype != np.float32 or (n is not None and g.shape[0] != n):
-            return None
-        f = C.fraction_coordinates
-        if not isinstance(f, (int, float, np.floating, np.integer)) or not np.isfinite(f):
-            return None
-        if fr is not None and f != fr:
-            return None
-        n, fr = g.shape[0], f
-    k = kept_count(fr, n)
-    return k if 0 < k < n else None
 
 
 def ef_batch_group(agg, n: int, m: int, dev: torch.device) -> int:
@@ -485,11 +628,8 @@ def ef_batch_fold(agg, clients, n: int, k: int, weights: np.ndarray, dev: torch.
         c.C._ef_buffers(n, dev, allocate=False)
     m = len(clients)
     gsz = ef_batch_group(agg, n, m, dev)
-    cache = agg.__dict__.setdefault("_ef_batch_packets", {})
-    packets = cache.get((n, dev))
-    if packets is None or len(packets) < gsz:
-        cache.clear()
-        packets = cache[(n, dev)] = codec.Packet.alloc_batch(n, gsz, L.FC_FMT_IDXVAL, dev, k=k)
+    packets = _cached(agg, "_ef_batch_packets", (n, dev), gsz,
+                      lambda count: codec.Packet.alloc_batch(n, count, L.FC_FMT_IDXVAL, dev, k=k))
     acc = torch.empty(n, dtype=torch.float32, device=dev)
     for gi, s in enumerate(range(0, m, gsz)):
         rows = clients[s:s + gsz]
@@ -548,47 +688,18 @@ def gram_route_k(agg, clients) -> int:
     otherwise ``NotImplementedError`` naming the condition that fails.  Touches no GPU (the
     budget is checked here only when ``device_budget_bytes`` is configured; :func:`gram_round`
     checks the default budget against the free memory)."""
-    def no(why: str):
-        raise NotImplementedError(f"the gram route (krum / pc_analysis='gram') needs {why}")
-    cfg = getattr(agg, "aggregation_config", None) or {}
-    if type(agg.gar) not in (FedAvg, Krum) + _LINEAR_RULES + _COORD_RULES:
+    no, gar = _gram_no, agg.gar
+    if type(gar) not in (FedAvg, Krum) + _LINEAR_RULES + _COORD_RULES:
         no("the device FedAvg or Krum (or spectral_gram / geometric_median / centered_clip / "
            "trimmed_mean / coordinate_median)")
-    if agg.num_hierarchies != 0:
-        no("no hierarchies (num_hierarchies == 0)")
-    if cfg.get("devices", DEFAULT_DEVICES) not in (None, 1):
-        no("one device")
-    w = getattr(agg.gar, "gradient_weights", None)
-    if w is not None and isinstance(agg.gar, CoordinateTrim):
-        raise ValueError(f"{type(agg.gar).__name__} is unweighted: gradient_weights must be None")
-    if w is not None and np.asarray(w).dtype != np.float32:
-        no("float32 GAR weights")
-    if len(clients) > L.FC_GRAM_MAX_M:
-        no(f"at most {L.FC_GRAM_MAX_M} clients (got {len(clients)})")
-    n, fr = None, None
-    for c in clients:
-        C, g = c.C, np.asarray(c.grad)
-        if getattr(C, "compression_function", None) != "top":
-            no("every client to compress with 'top'")
-        if getattr(C, "error_feedback", False):
-            no("'top' without error feedback")
-        if g.ndim != 1 or g.dtype != np.float32:
-            no("1-D float32 gradients")
-        if n is not None and g.shape[0] != n:
-            no("gradients of one length")
-        f = C.fraction_coordinates
-        if not isinstance(f, (int, float, np.floating, np.integer)) or not np.isfinite(f):
-            no("a finite fraction_coordinates")
-        if fr is not None and f != fr:
-            no("one common fraction_coordinates")
-        n, fr = g.shape[0], f
-    k = kept_count(fr, n)
-    if not 0 < k < n:
-        no(f"0 < k < n (k={k}, n={n})")
-    b = cfg.get("device_budget_bytes")
-    if b and gram_resident_bytes(n, len(clients), agg.gar) > int(b):
-        no(f"the round's packets to fit device_budget_bytes ({gram_resident_bytes(n, len(clients), agg.gar)}"
-           f" > {int(b)} bytes)")
+    _no_hierarchies(agg, no)
+    _one_device(agg, no)
+    if isinstance(gar, CoordinateTrim):
+        gar._unweighted()
+    _f32_weights(gar, no)
+    _at_most(len(clients), "clients", no)
+    n, k = _top_round(clients, False, no)
+    _fit(agg, gram_resident_bytes(n, len(clients), gar), no)
     return k
 
 
@@ -600,16 +711,9 @@ def gram_round(agg, clients, n: int, k: int, dev: torch.device) -> torch.Tensor:
     values to ``gar.Sigma_tracked`` for
     ``pc_analysis: "gram"`` (after the entry ``SpectralGram`` appends itself: two per round)."""
     m = len(clients)
-    need = gram_resident_bytes(n, m, agg.gar)
-    if need > _budget(agg, dev):
-        raise NotImplementedError("the gram route (krum / pc_analysis='gram') needs the round's packets "
-                                  f"to fit device_budget_bytes ({need} > {_budget(agg, dev)} bytes)")
-    cache = agg.__dict__.setdefault("_gram_packets", {})
-    packets = cache.get((n, dev))
-    if packets is None or len(packets) < m:
-        cache.clear()
-        packets = cache[(n, dev)] = codec.Packet.alloc_batch(n, m, L.FC_FMT_IDXVAL, dev, k=k)
-    pk = packets[:m]
+    _fit(agg, gram_resident_bytes(n, m, agg.gar), _gram_no, dev)
+    pk = _cached(agg, "_gram_packets", (n, dev), m,
+                 lambda count: codec.Packet.alloc_batch(n, count, L.FC_FMT_IDXVAL, dev, k=k))
     grads = [torch.from_numpy(np.ascontiguousarray(c.grad)).to(dev) for c in clients]
     codec.encode_top_batch(grads, k, packets=pk, check=False)
     codec.resolve(pk)
@@ -624,7 +728,7 @@ def _gram_family(agg, gar, pk) -> torch.Tensor:
     the "sign-gram" and "sign-trim" routes' on sign packets: ``codec.gram_sign``,
     ``codec.fold_sign`` and, through the coordinate-wise rules, ``codec.trimmed_mean_sign``)."""
     m = len(pk)
-    pc = getattr(agg, "analyze_pc", False) == "gram"
+    pc = _pc_gram(agg)
     sign = isinstance(pk[0], codec.SignPacket)
     if isinstance(gar, CoordinateTrim):
         out = gar.aggregate_packets(pk)
@@ -642,14 +746,17 @@ def _gram_family(agg, gar, pk) -> torch.Tensor:
     return out
 
 
-# ---- the "sign" route: a round of scaled-sign clients, only their N/8-byte packets resident ----
-def _sign_no(why: str):
-    raise NotImplementedError(f"the sign route (sign packets: fed_avg / sign_majority) needs {why}")
+def _pc_gram(agg) -> bool:
+    return getattr(agg, "analyze_pc", False) == "gram"
+
+
+# ---- rounds of scaled-sign clients: only their N/8-byte packets resident ----------------------
+_MAJORITY_TAIL = ": the majority vote reads every packet at once"
 
 
 def sign_packet_bytes(n: int) -> int:
     """Device bytes of one resident sign packet: its words and header, rounded up to 256."""
-    return (4 * int(L.load().fc_sign_words(n)) + L.HDR_BYTES + 255) & ~255
+    return codec.slab_bytes(4 * int(L.load().fc_sign_words(n)) + L.HDR_BYTES)
 
 
 def sign_route(agg, clients) -> bool:
@@ -666,112 +773,104 @@ def sign_route(agg, clients) -> bool:
     :func:`sign_trim_route` decides).  Touches no GPU (the budget is checked here only when
     ``device_budget_bytes`` is configured; :func:`sign_round` checks the default budget)."""
     gar = getattr(agg, "gar", None)
-    cfg = getattr(agg, "aggregation_config", None) or {}
     major = type(gar) is SignMajority
-    all_sign = all(getattr(c.C, "compression_function", None) == "sign" for c in clients)
-    if not all_sign:
+    if not _all_sign(clients):
         if major:
             _sign_no("every client to compress with 'sign'")
         return False
     if gram_wanted(agg):
-        if sign_geometry_wanted(agg):
-            return False                       # the "sign-gram" route's business (sign_gram_route)
-        if sign_trim_wanted(agg):
-            return False                       # the "sign-trim" route's business (sign_trim_route)
+        if sign_geometry_wanted(agg) or sign_trim_wanted(agg):
+            return False                       # the "sign-gram" / "sign-trim" route's business
         what = type(gar).__name__ if type(gar) is not FedAvg else "pc_analysis 'gram'"
         raise NotImplementedError(f"{what} has no consumer of sign packets: a round of 'sign' "
                                   "clients takes fed_avg or sign_majority")
-    if not major and (type(gar) is not FedAvg or cfg.get("sign_packets", True) is False):
+    if major:                                  # every failed condition is named
+        gar._unweighted()
+        n = _sign_conditions(agg, clients, _sign_no)
+        _fit(agg, len(clients) * sign_packet_bytes(n) + 8 * n, _sign_no, tail=_MAJORITY_TAIL)
+        return True
+    if type(gar) is not FedAvg or _config(agg).get("sign_packets", True) is False:
         return False
-
-    def no(why: str):
-        if major:
-            _sign_no(why)
-        return False
-
-    if major and gar.gradient_weights is not None:
-        raise ValueError("SignMajority is unweighted: gradient_weights must be None")
-    if not all(isinstance(c.C, Compression) for c in clients):
-        return no("every client to be the drop-in Compression")
-    if agg.num_hierarchies != 0:
-        return no("no hierarchies (num_hierarchies == 0)")
-    if cfg.get("devices", DEFAULT_DEVICES) not in (None, 1):
-        return no("one device")
-    w = getattr(gar, "gradient_weights", None)
-    if w is not None and np.asarray(w).dtype != np.float32:
-        return no("float32 GAR weights")
-    n = None
-    for c in clients:
-        g = np.asarray(c.grad)
-        if g.ndim != 1 or g.dtype != np.float32:
-            return no("1-D float32 gradients")
-        if n is not None and g.shape[0] != n:
-            return no("gradients of one length")
-        n = g.shape[0]
-    if n == 0:
-        return no("a gradient length n > 0")
-    b = cfg.get("device_budget_bytes")
-    if major and b and len(clients) * sign_packet_bytes(n) + 8 * n > int(b):
-        _sign_no(f"the round's packets to fit device_budget_bytes "
-                 f"({len(clients) * sign_packet_bytes(n) + 8 * n} > {int(b)} bytes): the majority "
-                 "vote reads every packet at once")
+    try:
+        _sign_conditions(agg, clients, _refused)
+    except _Refused:
+        return False                           # the generic routes take the round
     return True
+
+
+def _sign_residuals_ready(clients, n: int, dev: torch.device) -> None:
+    """Every residual of the round checked before one advances: a bad one raises here."""
+    for c in clients:
+        if c.C.error_feedback:
+            c.C._ef_buffers(n, dev, allocate=False)
+
+
+def _sign_encode(agg, part, n: int, dev: torch.device, count: int) -> list:
+    """``part`` (clients of a round that passed :func:`_sign_residuals_ready`, ``count`` of them
+    at the most) uploaded and encoded one at a time (``codec.encode_sign``) into the aggregator's
+    ``count`` cached sign packets; returns theirs.  With error feedback a client's residual
+    advances exactly once, committed after its encode was issued."""
+    slots = _cached(agg, "_sign_packets", (n, dev), count,
+                    lambda count: [codec.SignPacket.alloc(n, dev) for _ in range(count)])[:len(part)]
+    for c, slot in zip(part, slots):
+        g = torch.from_numpy(np.ascontiguousarray(c.grad)).to(dev)
+        if c.C.error_feedback:
+            res, spare = c.C._ef_buffers(n, dev)
+            _, new = codec.encode_sign(g, res, residual_out=spare, packet=slot)
+            c.C._ef_commit(res, new, True)
+        else:
+            codec.encode_sign(g, packet=slot)
+    return slots
 
 
 def sign_round(agg, clients, n: int, dev: torch.device) -> torch.Tensor:
     """One round on the "sign" route.  The clients are uploaded and encoded one at a time
-    (``codec.encode_sign``; with error feedback each client's residual advances exactly once,
-    committed after its encode was issued), so only their N/8-byte packets stay resident.
+    (:func:`_sign_encode`), so only their N/8-byte packets stay resident.
     ``FedAvg`` folds them in row order in groups sized by the budget, continuing the sum
     (``codec.fold_sign``: the "dense-fold" route's bits); ``SignMajority`` votes over all of them
     and raises ``NotImplementedError`` naming the budget when they do not fit."""
     gar, m = agg.gar, len(clients)
     major = type(gar) is SignMajority
-    per, budget = sign_packet_bytes(n), _budget(agg, dev)
-    room = budget - 8 * n                      # beside the aggregate and the gradient in flight
-    if major and m * per > room:
-        _sign_no(f"the round's packets to fit device_budget_bytes ({m * per + 8 * n} > {budget} "
-                 "bytes): the majority vote reads every packet at once")
-    group = m if major else int(max(1, min(m, 65535, room // per)))
-    for c in clients:                          # every residual checked before one advances
-        if c.C.error_feedback:
-            c.C._ef_buffers(n, dev, allocate=False)
+    per = sign_packet_bytes(n)
+    if major:
+        _fit(agg, m * per + 8 * n, _sign_no, dev, tail=_MAJORITY_TAIL)
+        group = m
+    else:                                      # beside the aggregate and the gradient in flight
+        group = int(max(1, min(m, 65535, (_budget(agg, dev) - 8 * n) // per)))
+    _sign_residuals_ready(clients, n, dev)
     w = None if major else gar._weights(m, np.float32)                # gar.py:37-42 (persisted)
-    cache = agg.__dict__.setdefault("_sign_packets", {})
-    slots = cache.get((n, dev))
-    if slots is None or len(slots) < group:
-        cache.clear()
-        slots = cache[(n, dev)] = [codec.SignPacket.alloc(n, dev) for _ in range(group)]
     out = torch.empty(n, dtype=torch.float32, device=dev)
     agg.sign_groups = 0
     for s in range(0, m, group):
-        part = clients[s:s + group]
-        for c, slot in zip(part, slots):
-            g = torch.from_numpy(np.ascontiguousarray(c.grad)).to(dev)
-            if c.C.error_feedback:
-                res, spare = c.C._ef_buffers(n, dev)
-                _, new = codec.encode_sign(g, res, residual_out=spare, packet=slot)
-                c.C._ef_commit(res, new, True)
-            else:
-                codec.encode_sign(g, packet=slot)
-        pk = slots[:len(part)]
+        pk = _sign_encode(agg, clients[s:s + group], n, dev, group)
         if major:
             gar.aggregate_packets(pk, out=out)
         else:
-            codec.fold_sign(pk, [float(x) for x in w[s:s + len(part)]], out=out, continue_sum=s > 0)
+            codec.fold_sign(pk, [float(x) for x in w[s:s + len(pk)]], out=out, continue_sum=s > 0)
         agg.sign_groups += 1
     return out
 
 
-# ---- the "sign-gram" route (opt-in): the Gram family's consumers on a round of sign packets ----
+def _sign_encode_resident(agg, clients, n: int, dev: torch.device) -> list:
+    """The round's clients encoded into sign packets that all stay resident."""
+    _sign_residuals_ready(clients, n, dev)
+    return _sign_encode(agg, clients, n, dev, len(clients))
+
+
+# ---- the opt-in "sign-gram" and "sign-trim" routes: all M sign packets resident ----------------
 def sign_geometry_wanted(agg) -> bool:
     """Is ``aggregation_config["sign_geometry"]`` set and the scheme one whose geometry sign
     packets can give: Krum, a linear rule, or the device FedAvg with ``pc_analysis: "gram"``?
     (The coordinate-wise rules need no geometry: their kernel over sign packets is behind
     ``"sign_trim"``, :func:`sign_trim_wanted`.)"""
-    cfg = getattr(agg, "aggregation_config", None) or {}
-    return (bool(cfg.get("sign_geometry", False)) and gram_wanted(agg)
+    return (bool(_config(agg).get("sign_geometry", False)) and gram_wanted(agg)
             and not isinstance(agg.gar, CoordinateTrim))
+
+
+def sign_trim_wanted(agg) -> bool:
+    """Is ``aggregation_config["sign_trim"]`` set and the scheme a coordinate-wise rule
+    (trimmed_mean, coordinate_median)?  The key does nothing for any other scheme."""
+    return bool(_config(agg).get("sign_trim", False)) and type(getattr(agg, "gar", None)) in _COORD_RULES
 
 
 def sign_gram_resident_bytes(n: int, m: int, packets_bytes: Optional[int] = None) -> int:
@@ -783,122 +882,6 @@ def sign_gram_resident_bytes(n: int, m: int, packets_bytes: Optional[int] = None
         packets_bytes = m * sign_packet_bytes(n)
     return (packets_bytes + 4 * n + 4 * n + int(lib.fc_sign_gram_workspace_bytes(n, m))
             + int(lib.fc_sign_dot_workspace_bytes(n, m)) + 8 * m * m)
-
-
-def sign_gram_route(agg, clients) -> bool:
-    """Does this round take the "sign-gram" route?  False without the key, under a scheme outside
-    :func:`sign_geometry_wanted`, or when not every client compresses with 'sign' (the other
-    routes decide).  Otherwise the conditions of :func:`sign_route`, at most ``FC_GRAM_MAX_M``
-    clients and, when ``device_budget_bytes`` is configured, the resident bytes within it: each
-    failure is a ``NotImplementedError`` naming the condition.  Touches no GPU."""
-    if not sign_geometry_wanted(agg):
-        return False
-    if not all(getattr(c.C, "compression_function", None) == "sign" for c in clients):
-        return False
-
-    def no(why: str):
-        raise NotImplementedError(f"the sign-gram route (sign_geometry) needs {why}")
-
-    cfg = getattr(agg, "aggregation_config", None) or {}
-    if not all(isinstance(c.C, Compression) for c in clients):
-        no("every client to be the drop-in Compression")
-    if agg.num_hierarchies != 0:
-        no("no hierarchies (num_hierarchies == 0)")
-    if cfg.get("devices", DEFAULT_DEVICES) not in (None, 1):
-        no("one device")
-    w = getattr(agg.gar, "gradient_weights", None)
-    if w is not None and np.asarray(w).dtype != np.float32:
-        no("float32 GAR weights")
-    n = None
-    for c in clients:
-        g = np.asarray(c.grad)
-        if g.ndim != 1 or g.dtype != np.float32:
-            no("1-D float32 gradients")
-        if n is not None and g.shape[0] != n:
-            no("gradients of one length")
-        n = g.shape[0]
-    if n == 0:
-        no("a gradient length n > 0")
-    m = len(clients)
-    if m > L.FC_GRAM_MAX_M:
-        no(f"at most {L.FC_GRAM_MAX_M} clients (got {m})")
-    b = cfg.get("device_budget_bytes")
-    if b and sign_gram_resident_bytes(n, m) > int(b):
-        no(f"the round's packets to fit device_budget_bytes ({sign_gram_resident_bytes(n, m)} > "
-           f"{int(b)} bytes)")
-    return True
-
-
-def sign_gram_round(agg, clients, n: int, dev: torch.device) -> torch.Tensor:
-    """One round on the "sign-gram" route: the clients are uploaded and encoded one at a time as
-    in :func:`sign_round` (with error feedback each residual advances exactly once), all M packets
-    stay resident, then the "gram" route's consumers run on them (:func:`_gram_family`)."""
-    m = len(clients)
-    need, budget = sign_gram_resident_bytes(n, m), _budget(agg, dev)
-    if need > budget:
-        raise NotImplementedError("the sign-gram route (sign_geometry) needs the round's packets to "
-                                  f"fit device_budget_bytes ({need} > {budget} bytes)")
-    return _gram_family(agg, agg.gar, _sign_encode_resident(agg, clients, n, dev))
-
-
-def _sign_encode_resident(agg, clients, n: int, dev: torch.device) -> list:
-    """The round's clients uploaded and encoded one at a time into the aggregator's cached sign
-    packets, all M of which stay resident (the "sign-gram" and "sign-trim" routes).  Every
-    residual is checked before one advances; each then advances exactly once."""
-    m = len(clients)
-    for c in clients:                          # every residual checked before one advances
-        if c.C.error_feedback:
-            c.C._ef_buffers(n, dev, allocate=False)
-    cache = agg.__dict__.setdefault("_sign_packets", {})
-    slots = cache.get((n, dev))
-    if slots is None or len(slots) < m:
-        cache.clear()
-        slots = cache[(n, dev)] = [codec.SignPacket.alloc(n, dev) for _ in range(m)]
-    pk = slots[:m]
-    for c, slot in zip(clients, pk):
-        g = torch.from_numpy(np.ascontiguousarray(c.grad)).to(dev)
-        if c.C.error_feedback:
-            res, spare = c.C._ef_buffers(n, dev)
-            _, new = codec.encode_sign(g, res, residual_out=spare, packet=slot)
-            c.C._ef_commit(res, new, True)
-        else:
-            codec.encode_sign(g, packet=slot)
-    return pk
-
-
-def _sign_wire_upload(agg, part, dev: torch.device) -> list:
-    """Validated sign payloads (``codec._sign_check``'s pairs) into one cached device slab, 256-byte
-    aligned each: the packets are views of it."""
-    cache = agg.__dict__.setdefault("_sign_wire", {})
-    offs = np.concatenate([[0], np.cumsum([(a.size + 255) & ~255 for a, _ in part])])
-    slab = cache.get("slab")
-    if slab is None or slab.device != dev or slab.numel() < int(offs[-1]):
-        cache.pop("slab", None)
-        slab = cache["slab"] = torch.empty(int(offs[-1]), dtype=torch.uint8, device=dev)
-    return [codec._sign_upload(a, h, dev, out=slab[int(o): int(o) + a.size])
-            for (a, h), o in zip(part, offs)]
-
-
-def sign_wire_gram_round(agg, hosts, n: int, dev: torch.device) -> torch.Tensor:
-    """aggregate_wire's round of validated sign payloads under ``sign_geometry``: all uploaded,
-    then the "gram" route's consumers on them (:func:`_gram_family`)."""
-    total = sum((a.size + 255) & ~255 for a, _ in hosts)
-    need, budget = sign_gram_resident_bytes(n, len(hosts), total), _budget(agg, dev)
-    if need > budget:
-        _wire_no(f"the round's sign packets to fit device_budget_bytes ({need} > {budget} bytes)")
-    return _gram_family(agg, agg.gar, _sign_wire_upload(agg, hosts, dev))
-
-
-# ---- the "sign-trim" route (opt-in): the coordinate-wise rules on a round of sign packets ----
-def _sign_trim_no(why: str):
-    raise NotImplementedError(f"the sign-trim route (sign_trim) needs {why}")
-
-
-def sign_trim_wanted(agg) -> bool:
-    """Is ``aggregation_config["sign_trim"]`` set and the scheme a coordinate-wise rule
-    (trimmed_mean, coordinate_median)?  The key does nothing for any other scheme."""
-    cfg = getattr(agg, "aggregation_config", None) or {}
-    return bool(cfg.get("sign_trim", False)) and type(getattr(agg, "gar", None)) in _COORD_RULES
 
 
 def sign_trim_resident_bytes(n: int, m: int, pc: bool = False,
@@ -917,8 +900,32 @@ def sign_trim_resident_bytes(n: int, m: int, pc: bool = False,
     return need
 
 
-def _pc_gram(agg) -> bool:
-    return getattr(agg, "analyze_pc", False) == "gram"
+def _sign_resident_bytes(agg, trim: bool, n: int, m: int, packets_bytes: Optional[int] = None) -> int:
+    if trim:
+        return sign_trim_resident_bytes(n, m, _pc_gram(agg), packets_bytes)
+    return sign_gram_resident_bytes(n, m, packets_bytes)
+
+
+def _sign_resident_route(agg, clients, trim: bool) -> bool:
+    """The conditions both resident routes ask of a round of 'sign' clients: those of
+    :func:`_sign_conditions` (``trim``: unweighted), at most ``FC_GRAM_MAX_M`` clients and, when
+    ``device_budget_bytes`` is configured, the resident bytes within it."""
+    if not _all_sign(clients):
+        return False
+    no = _sign_trim_no if trim else _sign_gram_no
+    n, m = _sign_conditions(agg, clients, no, unweighted=trim), len(clients)
+    _at_most(m, "clients", no)
+    _fit(agg, _sign_resident_bytes(agg, trim, n, m), no)
+    return True
+
+
+def sign_gram_route(agg, clients) -> bool:
+    """Does this round take the "sign-gram" route?  False without the key, under a scheme outside
+    :func:`sign_geometry_wanted`, or when not every client compresses with 'sign' (the other
+    routes decide).  Otherwise the conditions of :func:`sign_route`, at most ``FC_GRAM_MAX_M``
+    clients and, when ``device_budget_bytes`` is configured, the resident bytes within it: each
+    failure is a ``NotImplementedError`` naming the condition.  Touches no GPU."""
+    return sign_geometry_wanted(agg) and _sign_resident_route(agg, clients, False)
 
 
 def sign_trim_route(agg, clients) -> bool:
@@ -927,60 +934,26 @@ def sign_trim_route(agg, clients) -> bool:
     decide).  Otherwise the conditions of :func:`sign_gram_route`: each failure is a
     ``NotImplementedError`` naming the condition, and a ``gradient_weights`` that is not None is
     the rules' ``ValueError``.  Touches no GPU."""
-    if not sign_trim_wanted(agg):
-        return False
-    if not all(getattr(c.C, "compression_function", None) == "sign" for c in clients):
-        return False
-    no = _sign_trim_no
-    cfg = getattr(agg, "aggregation_config", None) or {}
-    if not all(isinstance(c.C, Compression) for c in clients):
-        no("every client to be the drop-in Compression")
-    if agg.num_hierarchies != 0:
-        no("no hierarchies (num_hierarchies == 0)")
-    if cfg.get("devices", DEFAULT_DEVICES) not in (None, 1):
-        no("one device")
-    if getattr(agg.gar, "gradient_weights", None) is not None:
-        raise ValueError(f"{type(agg.gar).__name__} is unweighted: gradient_weights must be None")
-    n = None
-    for c in clients:
-        g = np.asarray(c.grad)
-        if g.ndim != 1 or g.dtype != np.float32:
-            no("1-D float32 gradients")
-        if n is not None and g.shape[0] != n:
-            no("gradients of one length")
-        n = g.shape[0]
-    if n == 0:
-        no("a gradient length n > 0")
-    m = len(clients)
-    if m > L.FC_GRAM_MAX_M:
-        no(f"at most {L.FC_GRAM_MAX_M} clients (got {m})")
-    b = cfg.get("device_budget_bytes")
-    need = sign_trim_resident_bytes(n, m, _pc_gram(agg))
-    if b and need > int(b):
-        no(f"the round's packets to fit device_budget_bytes ({need} > {int(b)} bytes)")
-    return True
+    return sign_trim_wanted(agg) and _sign_resident_route(agg, clients, True)
 
 
-def sign_trim_round(agg, clients, n: int, dev: torch.device) -> torch.Tensor:
-    """One round on the "sign-trim" route: the clients are uploaded and encoded one at a time as
-    in :func:`sign_gram_round` (with error feedback each residual advances exactly once), all M
-    packets stay resident, then :func:`_gram_family` runs the rule on them
-    (``codec.trimmed_mean_sign``; ``codec.gram_sign`` only for ``pc_analysis: "gram"``)."""
-    need, budget = sign_trim_resident_bytes(n, len(clients), _pc_gram(agg)), _budget(agg, dev)
-    if need > budget:
-        _sign_trim_no(f"the round's packets to fit device_budget_bytes ({need} > {budget} bytes)")
-    return _gram_family(agg, agg.gar, _sign_encode_resident(agg, clients, n, dev))
+def _resident_round(agg, need: int, no, dev: torch.device, packets, what: str = "packets") -> torch.Tensor:
+    """One round whose packets all stay resident ("sign-gram", "sign-trim" and aggregate_wire's
+    Gram family): the default budget checked on the device, then ``packets()`` (the clients
+    encoded, or the payloads uploaded) and the "gram" route's consumers on them."""
+    _fit(agg, need, no, dev, what)
+    return _gram_family(agg, agg.gar, packets())
 
 
-def sign_wire_trim_round(agg, hosts, n: int, dev: torch.device) -> torch.Tensor:
-    """aggregate_wire's round of validated sign payloads under ``sign_trim``: all uploaded into
-    the cached slab, then :func:`_gram_family` (the bits of :func:`sign_trim_round`)."""
-    total = sum((a.size + 255) & ~255 for a, _ in hosts)
-    need = sign_trim_resident_bytes(n, len(hosts), _pc_gram(agg), total)
-    budget = _budget(agg, dev)
-    if need > budget:
-        _sign_trim_no(f"the round's sign packets to fit device_budget_bytes ({need} > {budget} bytes)")
-    return _gram_family(agg, agg.gar, _sign_wire_upload(agg, hosts, dev))
+def sign_resident_round(agg, clients, n: int, dev: torch.device, trim: bool) -> torch.Tensor:
+    """One round on the "sign-gram" (``trim``: the "sign-trim") route: the clients are uploaded and
+    encoded one at a time as in :func:`sign_round` (with error feedback each residual advances
+    exactly once), all M packets stay resident, then :func:`_gram_family` runs on them: the Gram
+    matrix from the bits and the rule, or ``codec.trimmed_mean_sign`` (``codec.gram_sign`` then
+    only for ``pc_analysis: "gram"``)."""
+    return _resident_round(agg, _sign_resident_bytes(agg, trim, n, len(clients)),
+                           _sign_trim_no if trim else _sign_gram_no, dev,
+                           lambda: _sign_encode_resident(agg, clients, n, dev))
 
 
 def sign_wire_round(agg, hosts, n: int, dev: torch.device) -> torch.Tensor:
@@ -988,26 +961,43 @@ def sign_wire_round(agg, hosts, n: int, dev: torch.device) -> torch.Tensor:
     returned for each): uploaded into one cached device slab and folded in groups
     (:func:`wire_fold_groups`, ``fed_avg``) or voted over, all resident (``sign_majority``)."""
     gar, m = agg.gar, len(hosts)
-    sizes = [a.size for a, _ in hosts]
-    budget = _budget(agg, dev)
     if type(gar) is SignMajority:
-        total = sum((b + 255) & ~255 for b in sizes)
-        if total + 4 * n > budget:
-            _wire_no(f"the round's sign packets to fit device_budget_bytes ({total + 4 * n} > "
-                     f"{budget} bytes): the majority vote reads every packet at once")
+        _fit(agg, sum(codec.slab_bytes(a.size) for a, _ in hosts) + 4 * n, _wire_no, dev, "sign packets",
+             _MAJORITY_TAIL)
         groups = [range(0, m)]
         wts = None
     else:
-        groups = wire_fold_groups(sizes, n, budget)
+        groups = wire_fold_groups([a.size for a, _ in hosts], n, _budget(agg, dev))
         wts = gar._weights(m, np.float32)                               # gar.py:37-42 (persisted)
     out = torch.empty(n, dtype=torch.float32, device=dev)
     for gi, g in enumerate(groups):
-        pk = _sign_wire_upload(agg, hosts[g.start:g.stop], dev)
+        pk = _slab_upload(agg, "_sign_wire", codec._sign_upload, hosts[g.start:g.stop], dev)
         if wts is None:
             gar.aggregate_packets(pk, out=out)
         else:
             codec.fold_sign(pk, [float(x) for x in wts[g.start:g.stop]], out=out, continue_sum=gi > 0)
     return out
+
+
+def round_route(agg, clients):
+    """Which of ``aggregate_grads``' packet routes the round takes, decided on the host (no GPU is
+    touched): ``(agg_path, k)`` with ``agg_path`` one of "gram", "sign-gram", "sign-trim", "sign"
+    and "ef-batch" (``k``: the common 'top' count of "gram" and "ef-batch", else None), or None
+    for the stream / dense tail.  A round that a scheme or an opt-in key claims but whose
+    conditions fail raises that route's refusal (no dense fallback).  The predicates are read in
+    this order, so a round of 'sign' clients under a scheme without a consumer of sign packets is
+    refused before the gram route's own conditions are read."""
+    sign = sign_route(agg, clients)
+    sign_gram = sign_gram_route(agg, clients)
+    sign_trim = sign_trim_route(agg, clients)
+    if sign_gram or sign_trim:
+        return ("sign-gram" if sign_gram else "sign-trim"), None
+    if gram_wanted(agg):
+        return "gram", gram_route_k(agg, clients)
+    if sign:
+        return "sign", None
+    k = ef_batch_k(agg, clients)
+    return None if k is None else ("ef-batch", k)
 
 
 def aggregate_grads(self, clients: List, input_feature: np.ndarray = None,
@@ -1021,53 +1011,26 @@ def aggregate_grads(self, clients: List, input_feature: np.ndarray = None,
         if ref is not None:                 # patched reference class: its own SVD analysis
             return ref(self, clients, input_feature, val_loader)
         raise NotImplementedError("pc_analysis (randomized SVD of G) is outside the hot path")
-    # Krum / pc_analysis "gram": a round outside the route's conditions raises here, before a
-    # GPU is touched (no dense fallback)
-    # a round of 'sign' clients: its own route, or NotImplementedError for a scheme without a
-    # consumer of sign packets (before the gram route's own conditions are read)
-    sign = sign_route(self, clients)
-    # opt-in ("sign_geometry"): the Gram family's consumers on a round of sign packets
-    sign_gram = sign_gram_route(self, clients)
-    # opt-in ("sign_trim"): the coordinate-wise rules on a round of sign packets
-    sign_trim = sign_trim_route(self, clients)
-    k_gram = (gram_route_k(self, clients)
-              if gram_wanted(self) and not sign_gram and not sign_trim else None)
+    # a packet route, or its refusal, is decided before a GPU is touched (no dense fallback)
+    route = round_route(self, clients)
     dev = _device_of(self)
     grad0 = np.asarray(clients[0].grad)
     n = grad0.shape[0]
     if any(np.asarray(c.grad).shape != (n,) for c in clients):
         raise ValueError("client gradients must share one length (aggregation.py:61)")
-    if k_gram is not None:
-        # the round's packets resident at once, their Gram matrix straight from them
-        self.agg_path = "gram"
+    if route is not None:
+        self.agg_path, k = route
         self.curr_G = None
-        self.agg_grad = gram_round(self, clients, n, k_gram, dev).cpu().numpy()
-        return
-    if sign_gram:
-        # every client a scaled-sign packet, all resident: Gram matrix from the bits, then the rule
-        self.agg_path = "sign-gram"
-        self.curr_G = None
-        self.agg_grad = sign_gram_round(self, clients, n, dev).cpu().numpy()
-        return
-    if sign_trim:
-        # every client a scaled-sign packet, all resident: the trimmed mean straight from the bits
-        self.agg_path = "sign-trim"
-        self.curr_G = None
-        self.agg_grad = sign_trim_round(self, clients, n, dev).cpu().numpy()
-        return
-    if sign:
-        # every client a scaled-sign packet: encoded one at a time, folded or voted from the bits
-        self.agg_path = "sign"
-        self.curr_G = None
-        self.agg_grad = sign_round(self, clients, n, dev).cpu().numpy()
-        return
-    k_ef = ef_batch_k(self, clients)
-    if k_ef is not None:
-        # opt-in: a round of error-feedback 'top' clients, batched (dense-fold's bits)
-        self.agg_path = "ef-batch"
-        self.curr_G = None
-        w = self.gar._weights(len(clients), np.float32)             # gar.py:37-42 (persisted)
-        self.agg_grad = ef_batch_fold(self, clients, n, k_ef, w, dev).cpu().numpy()
+        if self.agg_path == "gram":
+            out = gram_round(self, clients, n, k, dev)
+        elif self.agg_path == "sign":
+            out = sign_round(self, clients, n, dev)
+        elif self.agg_path == "ef-batch":           # dense-fold's bits
+            w = self.gar._weights(len(clients), np.float32)         # gar.py:37-42 (persisted)
+            out = ef_batch_fold(self, clients, n, k, w, dev)
+        else:
+            out = sign_resident_round(self, clients, n, dev, trim=self.agg_path == "sign-trim")
+        self.agg_grad = out.cpu().numpy()
         return
     device_gar = hasattr(self.gar, "aggregate_packets")
     w = getattr(self.gar, "gradient_weights", None)
@@ -1080,8 +1043,7 @@ def aggregate_grads(self, clients: List, input_feature: np.ndarray = None,
     streamable = device_gar and all_f32 and f32_weights and n > 0
     if streamable:
         # device permutations chain through one device state block: one device only
-        cfg = getattr(self, "aggregation_config", None) or {}
-        want_perm = bool(cfg.get("device_permutation", DEVICE_PERM))
+        want_perm = bool(_config(self).get("device_permutation", DEVICE_PERM))
         plan = row_plan(clients, n, device_perm=want_perm and len(stream_devices(self)) == 1)
     if plan is not None:
         # streamed from the host gradients, G never built (rows live group by group)
@@ -1159,10 +1121,6 @@ def wire_resident_bytes(n: int, m: int, wire_total: int, gar=None) -> int:
             + _trim_ws_bytes(n, m, gar))
 
 
-def _wire_no(why: str):
-    raise NotImplementedError(f"aggregate_wire needs {why}")
-
-
 def wire_fold_groups(sizes, n: int, budget_bytes: int) -> List[range]:
     """The payloads of a ``"wire_fold"`` round cut into consecutive groups, greedily: a group's
     sizes, each rounded up to 256 bytes (its place in the device slab), plus ``4 n`` for the
@@ -1173,7 +1131,7 @@ def wire_fold_groups(sizes, n: int, budget_bytes: int) -> List[range]:
     room = int(budget_bytes) - 4 * int(n)
     groups, first, used = [], 0, 0
     for i, b in enumerate(sizes):
-        r = (int(b) + 255) & ~255
+        r = codec.slab_bytes(b)
         if r > room:
             _wire_no(f"payload {i} and the aggregate to fit device_budget_bytes "
                      f"({r + 4 * int(n)} > {int(budget_bytes)} bytes)")
@@ -1186,128 +1144,14 @@ def wire_fold_groups(sizes, n: int, budget_bytes: int) -> List[range]:
     return groups
 
 
-def aggregate_wire(self, payloads, n: Optional[int] = None) -> None:
-    """A round from the clients' wire packets (``Compression.compress_wire``; include/fedcodec.h)
-    instead of their gradients: every payload is validated on the host (``fc_wire_validate``, the
-    check of ``codec.wire_from_host``: ``ValueError`` with the reason, before any of the round
-    reaches the GPU), uploaded, unpacked
-    into slotted packets and aggregated.  Sets ``agg_grad`` (host array), ``agg_path = "wire"``
-    and ``curr_G = None``.
-
-    * ``fed_avg``: any number of payloads, folded in row order in groups sized by the device
-      budget; bit-equal to the "stream" route of ``aggregate_grads`` on the same clients.
-      With ``aggregation_config["wire_fold"] = True`` (default ``False``) a group's payloads are
-      uploaded and folded as they are (``codec.fold_wire``): no slotted packets are reserved or
-      written, the groups are :func:`wire_fold_groups` of the payload sizes, the bits are the
-      same and ``agg_path = "wire-fold"``.  The key leaves the Gram family below untouched:
-      those consumers read slotted packets, so they still unpack and answer ``"wire"``.
-    * ``krum``, ``spectral_gram`` / ``geometric_median`` / ``centered_clip``, ``trimmed_mean`` /
-      ``coordinate_median`` and
-      ``pc_analysis: "gram"``: at most ``FC_GRAM_MAX_M`` payloads, all resident within the budget;
-      ``codec.gram`` then ``gar.aggregate_packets`` exactly as the "gram" route does.
-    * payloads that all carry the sign magic (``Compression.compress_wire`` of 'sign' clients):
-      validated by ``fc_sign_wire_validate``, uploaded and folded in groups (``fed_avg``,
-      ``codec.fold_sign``) or voted over, all resident (``sign_majority``), with ``agg_path =
-      "wire-sign"``; the other schemes and a round that mixes the two payload kinds raise.
-      With ``aggregation_config["sign_geometry"] = True`` (default absent) ``krum``, the linear
-      rules and ``pc_analysis: "gram"`` take such a round too: at most ``FC_GRAM_MAX_M`` payloads,
-      all resident, ``codec.gram_sign`` then the "gram" route's consumers, ``agg_path =
-      "wire-sign-gram"``, the bits of ``aggregate_grads``' "sign-gram" route on the same clients.
-      With ``aggregation_config["sign_trim"] = True`` (default absent) ``trimmed_mean`` and
-      ``coordinate_median`` take such a round: at most ``FC_GRAM_MAX_M`` payloads, all resident,
-      ``codec.trimmed_mean_sign``, ``agg_path = "wire-sign-trim"``, the bits of
-      ``aggregate_grads``' "sign-trim" route on the same clients.
-    Hierarchies, payloads of differing n and a round that does not fit raise
-    ``NotImplementedError`` naming the condition."""
-    no = _wire_no
-    payloads = list(payloads)
-    m = len(payloads)
-    if m == 0:
-        raise Exception('Client List is Empty')
-    if self.analyze_pc is True:
-        no("pc_analysis off or 'gram' (the randomized SVD of G is outside the hot path)")
-    if self.num_hierarchies != 0:
-        no("no hierarchies (num_hierarchies == 0)")
-    gar = self.gar
-    cfg = getattr(self, "aggregation_config", None) or {}
-    kinds = [codec.is_sign_payload(raw) for raw in payloads]
-    if any(kinds):
-        # ---- a round of sign payloads: validated on the host, folded or voted ("wire-sign") ----
-        if not all(kinds):
-            no("payloads of one kind (the round mixes sign packets and 'top' wire packets)")
-        geometry = sign_geometry_wanted(self)
-        trim = sign_trim_wanted(self)
-        if (type(gar) not in (FedAvg, SignMajority) or gram_wanted(self)) and not geometry and not trim:
-            no("fed_avg or sign_majority for sign packets (Krum, the linear rules, the trim rules "
-               "and pc_analysis 'gram' have no consumer of sign packets)")
-        if cfg.get("devices", DEFAULT_DEVICES) not in (None, 1):
-            no("one device")
-        w = getattr(gar, "gradient_weights", None)
-        if w is not None and type(gar) is SignMajority:
-            raise ValueError("SignMajority is unweighted: gradient_weights must be None")
-        if w is not None and trim:
-            raise ValueError(f"{type(gar).__name__} is unweighted: gradient_weights must be None")
-        if w is not None and np.asarray(w).dtype != np.float32:
-            no("float32 GAR weights")
-        if geometry and m > L.FC_GRAM_MAX_M:
-            no(f"at most {L.FC_GRAM_MAX_M} payloads for the sign-gram route (got {m})")
-        if trim and m > L.FC_GRAM_MAX_M:
-            _sign_trim_no(f"at most {L.FC_GRAM_MAX_M} payloads (got {m})")
-        hosts = []
-        for i, raw in enumerate(payloads):
-            try:
-                a, h = codec._sign_check(raw)
-            except ValueError as e:
-                raise ValueError(f"payload {i}: {e}") from None
-            hn = int(h.pkt.n)
-            if n is None:
-                n = hn
-            if hn != int(n):
-                no(f"payloads of one length n (payload {i} has n = {hn}, not {int(n)})")
-            hosts.append((a, h))
-        self.curr_G = None
-        if geometry:
-            # opt-in ("sign_geometry"): all resident, the Gram family's consumers on the bits
-            total = sum((a.size + 255) & ~255 for a, _ in hosts)
-            b = cfg.get("device_budget_bytes")
-            if b and sign_gram_resident_bytes(int(n), m, total) > int(b):
-                no(f"the round's sign packets to fit device_budget_bytes "
-                   f"({sign_gram_resident_bytes(int(n), m, total)} > {int(b)} bytes)")
-            self.agg_path = "wire-sign-gram"
-            self.agg_grad = sign_wire_gram_round(self, hosts, int(n), _device_of(self)).cpu().numpy()
-            return
-        if trim:
-            # opt-in ("sign_trim"): all resident, the trimmed mean straight from the bits
-            total = sum((a.size + 255) & ~255 for a, _ in hosts)
-            b = cfg.get("device_budget_bytes")
-            need = sign_trim_resident_bytes(int(n), m, _pc_gram(self), total)
-            if b and need > int(b):
-                _sign_trim_no(f"the round's sign packets to fit device_budget_bytes ({need} > "
-                              f"{int(b)} bytes)")
-            self.agg_path = "wire-sign-trim"
-            self.agg_grad = sign_wire_trim_round(self, hosts, int(n), _device_of(self)).cpu().numpy()
-            return
-        self.agg_path = "wire-sign"
-        self.agg_grad = sign_wire_round(self, hosts, int(n), _device_of(self)).cpu().numpy()
-        return
-    family = gram_wanted(self)
-    if not family and type(gar) is not FedAvg:
-        no("the device FedAvg, Krum, spectral_gram, geometric_median, centered_clip, trimmed_mean "
-           "or coordinate_median")
-    if cfg.get("devices", DEFAULT_DEVICES) not in (None, 1):
-        no("one device")
-    w = getattr(gar, "gradient_weights", None)
-    if w is not None and isinstance(gar, CoordinateTrim):
-        raise ValueError(f"{type(gar).__name__} is unweighted: gradient_weights must be None")
-    if w is not None and np.asarray(w).dtype != np.float32:
-        no("float32 GAR weights")
-    if family and m > L.FC_GRAM_MAX_M:
-        no(f"at most {L.FC_GRAM_MAX_M} payloads for the gram route (got {m})")
-    # ---- the host's part: every payload validated, one common n ----
-    hosts, total = [], 0
+def _validated(payloads, check, n: Optional[int], no):
+    """Every payload through ``check`` (``codec._wire_check`` / ``codec._sign_check``) on the host:
+    (the ``(bytes, header)`` pairs, their common n).  A bad payload is a ``ValueError`` naming its
+    position and the reason."""
+    hosts = []
     for i, raw in enumerate(payloads):
         try:
-            a, h = codec._wire_check(raw)
+            a, h = check(raw)
         except ValueError as e:
             raise ValueError(f"payload {i}: {e}") from None
         hn = int(h.pkt.n)
@@ -1316,45 +1160,99 @@ def aggregate_wire(self, payloads, n: Optional[int] = None) -> None:
         if hn != int(n):
             no(f"payloads of one length n (payload {i} has n = {hn}, not {int(n)})")
         hosts.append((a, h))
-        total += (a.size + 255) & ~255
-    n = int(n)
-    b = cfg.get("device_budget_bytes")
-    if family and b and wire_resident_bytes(n, m, total, gar) > int(b):
-        no(f"the round's packets to fit device_budget_bytes ({wire_resident_bytes(n, m, total, gar)}"
-           f" > {int(b)} bytes)")
-    # ---- the device's part ----
-    dev = _device_of(self)
-    self.agg_path = "wire"
-    self.curr_G = None
-    cache = self.__dict__.setdefault("_wire_packets", {})
+    return hosts, int(n)
 
-    def packets_for(count: int):
-        pk = cache.get((n, dev))
-        if pk is None or len(pk) < count:
-            for key in [k for k in cache if k != "slab"]:   # one shape at a time
-                del cache[key]
-            pk = cache[(n, dev)] = codec.Packet.alloc_batch(n, count, L.FC_FMT_IDXVAL, dev)
-        return pk[:count]
+
+def aggregate_wire(self, payloads, n: Optional[int] = None) -> None:
+    """A round from the clients' wire packets (``Compression.compress_wire``; include/fedcodec.h)
+    instead of their gradients: the "wire*" rows of the module's table.  Every payload is
+    validated on the host (``fc_wire_validate`` / ``fc_sign_wire_validate``: ``ValueError`` with
+    the payload's position and the reason) and every condition that needs no GPU is checked
+    before any of the round reaches it.  Sets ``agg_grad`` (host array), ``agg_path`` and
+    ``curr_G = None``.
+
+    * 'top' payloads under ``fed_avg``: any number, folded in row order in groups sized by the
+      device budget ("wire": unpacked into slotted packets, :func:`wire_group`; "wire-fold":
+      folded as they are, :func:`wire_fold_groups`); bit-equal to the "stream" route of
+      ``aggregate_grads`` on the same clients.
+    * 'top' payloads under a scheme of :func:`gram_wanted` ("wire", whatever ``"wire_fold"``
+      says: those consumers read slotted packets), sign payloads under ``"sign_geometry"``
+      ("wire-sign-gram") or ``"sign_trim"`` ("wire-sign-trim"): at most ``FC_GRAM_MAX_M``
+      payloads, all resident within the budget, then the "gram" route's consumers
+      (:func:`_gram_family`): the bits of ``aggregate_grads``' "gram", "sign-gram" and "sign-trim"
+      routes on the same clients.
+    * sign payloads under ``fed_avg`` (folded in groups, ``codec.fold_sign``) or ``sign_majority``
+      (voted over, all resident): "wire-sign".  Every other scheme refuses sign payloads, and a
+      round that mixes the two payload kinds is refused.
+    Hierarchies, several devices, payloads of differing n and a round that does not fit raise
+    ``NotImplementedError`` naming the condition."""
+    no = _wire_no
+    payloads = list(payloads)
+    m = len(payloads)
+    if m == 0:
+        raise Exception('Client List is Empty')
+    if self.analyze_pc is True:
+        no("pc_analysis off or 'gram' (the randomized SVD of G is outside the hot path)")
+    _no_hierarchies(self, no)
+    gar = self.gar
+    kinds = [codec.is_sign_payload(raw) for raw in payloads]
+    sign = any(kinds)
+    trim = sign and sign_trim_wanted(self)
+    if sign:
+        if not all(kinds):
+            no("payloads of one kind (the round mixes sign packets and 'top' wire packets)")
+        family = sign_geometry_wanted(self) or trim
+        if (type(gar) not in (FedAvg, SignMajority) or gram_wanted(self)) and not family:
+            no("fed_avg or sign_majority for sign packets (Krum, the linear rules, the trim rules "
+               "and pc_analysis 'gram' have no consumer of sign packets)")
+        what, many = "sign packets", "payloads" if trim else "payloads for the sign-gram route"
+    else:
+        family = gram_wanted(self)
+        if not family and type(gar) is not FedAvg:
+            no("the device FedAvg, Krum, spectral_gram, geometric_median, centered_clip, trimmed_mean "
+               "or coordinate_median")
+        what, many = "packets", "payloads for the gram route"
+    family_no = _sign_trim_no if trim else no      # the sign-trim route names its own refusals
+    _one_device(self, no)
+    if type(gar) is SignMajority or isinstance(gar, CoordinateTrim):
+        gar._unweighted()
+    _f32_weights(gar, no)
+    if family:
+        _at_most(m, many, family_no)
+    # ---- the host's part: every payload validated, one common n, a configured budget ----
+    hosts, n = _validated(payloads, codec._sign_check if sign else codec._wire_check, n, no)
+    if sign:
+        self.curr_G = None
+    if family:
+        total = sum(codec.slab_bytes(a.size) for a, _ in hosts)
+        need = (_sign_resident_bytes(self, trim, n, m, total) if sign
+                else wire_resident_bytes(n, m, total, gar))
+        _fit(self, need, family_no, what=what)
+    # ---- the device's part ----
+    if sign:
+        self.agg_path = "wire-sign" + ("" if not family else "-trim" if trim else "-gram")
+    dev = _device_of(self)
+    if not sign:
+        self.agg_path = "wire"
+        self.curr_G = None
 
     def upload(part):
         """The payloads of one group into one cached device slab (256-byte aligned each)."""
-        offs = np.concatenate([[0], np.cumsum([(a.size + 255) & ~255 for a, _ in part])])
-        slab = cache.get("slab")
-        if slab is None or slab.device != dev or slab.numel() < int(offs[-1]):
-            cache.pop("slab", None)
-            slab = cache["slab"] = torch.empty(int(offs[-1]), dtype=torch.uint8, device=dev)
-        return [codec._wire_upload(a, h, dev, out=slab[int(o): int(o) + a.size])
-                for (a, h), o in zip(part, offs)]
+        return _slab_upload(self, "_wire_packets", codec._wire_upload, part, dev)
 
-    if family:
-        need = wire_resident_bytes(n, m, total, gar)
-        if need > _budget(self, dev):
-            no(f"the round's packets to fit device_budget_bytes ({need} > {_budget(self, dev)} bytes)")
-        wires = upload(hosts)
-        pk = codec.unpack(wires, packets_for(m))
-        del wires
-        out = _gram_family(self, gar, pk)
-    elif cfg.get("wire_fold", False):
+    def packets_for(count: int):
+        return _cached(self, "_wire_packets", (n, dev), count,
+                       lambda count: codec.Packet.alloc_batch(n, count, L.FC_FMT_IDXVAL, dev))
+
+    if sign and family:
+        out = _resident_round(self, need, family_no, dev, what=what, packets=lambda: _slab_upload(
+            self, "_sign_wire", codec._sign_upload, hosts, dev))
+    elif sign:
+        out = sign_wire_round(self, hosts, n, dev)
+    elif family:
+        out = _resident_round(self, need, no, dev,
+                              lambda: codec.unpack(upload(hosts), packets_for(m)))
+    elif _config(self).get("wire_fold", False):
         wts = gar._weights(m, np.float32)                           # gar.py:37-42 (persisted)
         groups = wire_fold_groups([a.size for a, _ in hosts], n, _budget(self, dev))
         self.agg_path = "wire-fold"
@@ -1393,7 +1291,7 @@ class Aggregator:
         self.gar = self.__get_gar()
         self.curr_G = None
         self.agg_grad = None
-        self.agg_path = None                # "stream" | "dense-fold" | "dense" | "ef-batch" | "gram" | "sign" | "sign-gram" | "sign-trim" | "wire" | "wire-fold" | "wire-sign" | "wire-sign-gram" | "wire-sign-trim": the last call's path
+        self.agg_path = None                # the last call's route: a row of the module docstring's tables
         self.agg_draws = None               # streamed np.random draws: "device-mt" | "device-perm" | "host" | None
         self.analyze_pc = self.aggregation_config.get("pc_analysis", False)
         self.num_hierarchies = self.aggregation_config.get("num_hierarchies", 0)

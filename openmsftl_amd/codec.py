@@ -1092,6 +1092,11 @@ def pack_into(packets: Sequence[Packet], buffers: Sequence[torch.Tensor],
     return [L.WireHdr.from_buffer_copy(raw[i].tobytes()) for i in range(m)]
 
 
+def slab_bytes(nbytes: int) -> int:
+    """Bytes rounded up to 256: the room one packet takes in a device slab of several."""
+    return (int(nbytes) + 255) & ~255
+
+
 def pack(packets, entries=None):
     """The wire form of one idx/val packet or of a sequence of them (one launch chain):
     a :class:`WirePacket`, or a list of them.  Only the entries the decoders keep are packed.
@@ -1118,7 +1123,7 @@ def pack(packets, entries=None):
                 ent[i] = int(t)
     lib = L.load()
     caps = [int(lib.fc_wire_bytes(n, min(e, n))) for e in ent]
-    offs = np.concatenate([[0], np.cumsum([(c + 255) & ~255 for c in caps])]).astype(np.int64)
+    offs = np.concatenate([[0], np.cumsum([slab_bytes(c) for c in caps])]).astype(np.int64)
     slab = torch.empty(int(offs[-1]), dtype=torch.uint8, device=dev)
     bufs = [slab[int(offs[i]): int(offs[i]) + caps[i]] for i in range(m)]
     hdrs = pack_into(pk, bufs)

@@ -87,6 +87,11 @@ class GAR:
             raise TypeError(f"gradient_weights must be float32 or float64 (got {w.dtype})")
         return w
 
+    def _unweighted(self) -> None:
+        """The check of a rule that takes no weights (CoordinateTrim, SignMajority)."""
+        if self.gradient_weights is not None:
+            raise ValueError(f"{type(self).__name__} is unweighted: gradient_weights must be None")
+
     def weighted_average(self, stacked_grad):
         """gar.py:32-46 for an (M, N) float32/float64 G (NumPy array or CUDA tensor).  The
         result has NumPy's promoted dtype of G and the weights; it is a CUDA tensor for a CUDA
@@ -474,8 +479,7 @@ class CoordinateTrim(GAR):
                                   "dense G is not taken")
 
     def aggregate_packets(self, packets: Sequence["codec.Packet"], out=None) -> torch.Tensor:
-        if self.gradient_weights is not None:
-            raise ValueError(f"{type(self).__name__} is unweighted: gradient_weights must be None")
+        self._unweighted()
         sign = _sign_round(packets)
         self.trim = self._trim_of(len(packets))
         if sign:
@@ -563,8 +567,7 @@ class SignMajority(GAR):
                                   "the Aggregator's sign route); a dense G is not taken")
 
     def aggregate_packets(self, packets: Sequence["codec.SignPacket"], out=None) -> torch.Tensor:
-        if self.gradient_weights is not None:
-            raise ValueError("SignMajority is unweighted: gradient_weights must be None")
+        self._unweighted()
         packets = list(packets)
         if not packets or not all(isinstance(p, codec.SignPacket) for p in packets):
             raise TypeError("SignMajority votes over sign packets (codec.encode_sign)")
