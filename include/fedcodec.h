@@ -568,14 +568,39 @@ int fc_qsgd_decode_accumulate(const fc_packet_view* views_dev, int m, uint64_t n
  *   launches bring the words to the waves: 0 scalar loads and 1 vector loads with v_readlane
  *   (the 64-bit word wave-uniform, used as a lane mask), 2 one word per lane (the default: the
  *   fastest measured), -1 the default.  The results do not depend on it.
+ * fc_sign_encode_batch: fc_sign_encode for m clients of one length n, 1 <= m <= 65535.  Client c's
+ *   header (all 96 bytes), its fc_sign_words(n) words (tail bits and pad words zero) and its
+ *   res_out are, byte for byte, what fc_sign_encode writes for jobs[c]'s pointers.  jobs_dev is a
+ *   DEVICE array (8-B aligned), so the library cannot look inside it: has_res_in / has_res_out say
+ *   what the WHOLE batch carries (a job's res_in / res_out is then non-NULL in every job, else
+ *   ignored); 16-B alignment of every g / res_in / res_out / words, their length, that a job's
+ *   res_out overlaps no g / res_in / res_out of the batch, and that words and headers are distinct
+ *   per job, are the caller's contract.  Without res_out ONE launch for all m clients: the norm
+ *   pass's grid and loop per client (client = blockIdx.y), which also ballots and stores the words
+ *   of every 256 elements it reads, so g (and res_in) are read once: 4N (8N) + N/8 bytes per
+ *   client.  With res_out a second launch for all m streams e', each client's s read from its own
+ *   header.  No workgroup waits for another; stream-ordered, no allocation, no host
+ *   synchronisation.  ws: fc_sign_batch_workspace_bytes(n, m) bytes (m lone workspaces; monotone
+ *   in m), 8-B aligned, zeroed once (self-cleaning afterwards), one per stream.
  * Argument errors (NULL, n, m, alignment, overlap, n_words: FC_ERR_ARG; a short workspace:
  *   FC_ERR_WORKSPACE) are reported before the GPU is touched. */
+typedef struct fc_sign_job {
+  const float*   g;        /* gradient, n floats, 16-B aligned                                  */
+  const float*   res_in;   /* residual e, or NULL (then NULL for every job of the batch)        */
+  float*         res_out;  /* new residual e', or NULL (then NULL for every job of the batch)   */
+  uint32_t*      words;    /* >= fc_sign_words(n) uint32, 16-B aligned                          */
+  fc_packet_hdr* hdr;
+  uint64_t       reserved; /* 0 */
+} fc_sign_job;             /* 48 bytes */
 uint64_t fc_sign_words(uint64_t n);
 size_t fc_sign_workspace_bytes(uint64_t n);
 int fc_sign_encode(const float* g, const float* res_in /* NULL: none */,
                    float* res_out /* NULL: not wanted */, uint64_t n, uint32_t* words,
                    uint64_t n_words, fc_packet_hdr* hdr, void* ws, size_t ws_bytes,
                    fc_stream_t stream);
+size_t fc_sign_batch_workspace_bytes(uint64_t n, int m);
+int fc_sign_encode_batch(const fc_sign_job* jobs_dev, int m, uint64_t n, int has_res_in,
+                         int has_res_out, void* ws, size_t ws_bytes, fc_stream_t stream);
 int fc_sign_decode(const fc_packet_view* pkt, uint64_t n, float* out, fc_stream_t stream);
 int fc_sign_fold(const fc_packet_view* views_dev, int m, uint64_t n, float* out, int continue_sum,
                  fc_stream_t stream);

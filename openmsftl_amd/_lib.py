@@ -66,6 +66,12 @@ class EfJob(ctypes.Structure):
     _fields_ = [("res_in", ctypes.c_void_p), ("res_out", ctypes.c_void_p)]
 
 
+class SignJob(ctypes.Structure):
+    """fc_sign_job: one client of fc_sign_encode_batch."""
+    _fields_ = [("g", ctypes.c_void_p), ("res_in", ctypes.c_void_p), ("res_out", ctypes.c_void_p),
+                ("words", ctypes.c_void_p), ("hdr", ctypes.c_void_p), ("reserved", ctypes.c_uint64)]
+
+
 class PermState(ctypes.Structure):
     """fc_perm_state: the device state block of fc_mt_permutation."""
     _fields_ = [("key", ctypes.c_uint32 * 624), ("pos", ctypes.c_uint32),
@@ -100,6 +106,7 @@ assert ctypes.sizeof(PermState) == 2520
 assert ctypes.sizeof(PacketHdr) == HDR_BYTES
 assert ctypes.sizeof(EncodeJob) == 64
 assert ctypes.sizeof(EfJob) == 16
+assert ctypes.sizeof(SignJob) == 48
 assert ctypes.sizeof(PacketView) == 56
 
 _u64, _i32, _sz, _vp, _dbl = (ctypes.c_uint64, ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p,
@@ -158,6 +165,8 @@ SIGNATURES = {
     "fc_sign_words": (_u64, [_u64]),
     "fc_sign_workspace_bytes": (_sz, [_u64]),
     "fc_sign_encode": (_i32, [_vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _sz, _vp]),
+    "fc_sign_batch_workspace_bytes": (_sz, [_u64, _i32]),
+    "fc_sign_encode_batch": (_i32, [_vp, _i32, _u64, _i32, _i32, _vp, _sz, _vp]),
     "fc_sign_decode": (_i32, [ctypes.POINTER(PacketView), _u64, _vp, _vp]),
     "fc_sign_fold": (_i32, [_vp, _i32, _u64, _vp, _i32, _vp]),
     "fc_sign_vote": (_i32, [_vp, _i32, _u64, ctypes.c_float, _vp, _vp]),

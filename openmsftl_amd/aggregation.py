@@ -58,6 +58,10 @@ hierarchies, one device, float32 or no GAR weights, 1-D float32 gradients (paylo
 "wire-sign-trim"  the same, M <= 128, the schemes of "sign-trim"    ``sign_trim``         as "sign-trim"
 ================  ================================================  ====================  ====================================
 
+* ``batched_sign_encode`` (opt-in) names no route: on "sign", "sign-gram" and "sign-trim" it uploads
+  the clients in sub-batches (:func:`sign_encode_group`) and encodes those without error feedback
+  in one ``codec.encode_sign_batch`` call per sub-batch (:func:`_sign_encode_batched`); the bits,
+  the residuals and ``agg_path`` are those of the round without it.
 * "stream": the host gradients go through the ring (openmsftl_amd/pipeline.py): H2D, each row made
   on the device (top-k packets, mask packets whose masks are np.random's own draws in row order,
   made on the host or, :data:`DEVICE_MT` / :data:`DEVICE_PERM`, on the device, or the dense
@@ -805,13 +809,55 @@ def _sign_residuals_ready(clients, n: int, dev: torch.device) -> None:
             c.C._ef_buffers(n, dev, allocate=False)
 
 
+#: clients per sub-batch of the batched sign encode, at the most
+SIGN_ENCODE_GROUP = 64
+
+
+def sign_encode_group(agg, n: int, count: int, dev: torch.device) -> int:
+    """Clients per sub-batch of ``"batched_sign_encode"``: as many uploaded gradients (4N each) as
+    fit in the budget beside what the route counts without the key apart from its one gradient
+    in flight (the ``count`` packets and the aggregate), at most ``SIGN_ENCODE_GROUP`` and at
+    least one."""
+    fit = (_budget(agg, dev) - count * sign_packet_bytes(n) - 4 * n) // (4 * n)
+    return int(max(1, min(SIGN_ENCODE_GROUP, count, fit)))
+
+
+def _sign_encode_batched(agg, part, slots, n: int, dev: torch.device, count: int) -> None:
+    """:func:`_sign_encode` under ``aggregation_config["batched_sign_encode"]``: ``part`` in row
+    order in sub-batches of :func:`sign_encode_group` clients; a sub-batch is uploaded and its
+    clients without error feedback go through ONE ``codec.encode_sign_batch`` call (one read of
+    each gradient).  Its error-feedback clients keep the lone ``codec.encode_sign``, each committed
+    after its encode was issued: the batched form that also writes the new residuals measured
+    slower than the lone calls at 32 x 128 M.  The packets' and residuals'
+    bits are those of the lone calls; ``agg.sign_encode_calls`` counts the batched library calls
+    of the round."""
+    gsz = sign_encode_group(agg, n, count, dev)
+    for s in range(0, len(part), gsz):
+        rows = list(zip(part[s:s + gsz], slots[s:s + gsz]))
+        grads = [torch.from_numpy(np.ascontiguousarray(c.grad)).to(dev) for c, _ in rows]
+        plain = [i for i, (c, _) in enumerate(rows) if not c.C.error_feedback]
+        if plain:
+            codec.encode_sign_batch([grads[i] for i in plain], packets=[rows[i][1] for i in plain])
+            agg.sign_encode_calls += 1
+        for g, (c, slot) in zip(grads, rows):
+            if c.C.error_feedback:
+                res, spare = c.C._ef_buffers(n, dev)
+                _, new = codec.encode_sign(g, res, residual_out=spare, packet=slot)
+                c.C._ef_commit(res, new, True)
+
+
 def _sign_encode(agg, part, n: int, dev: torch.device, count: int) -> list:
     """``part`` (clients of a round that passed :func:`_sign_residuals_ready`, ``count`` of them
     at the most) uploaded and encoded one at a time (``codec.encode_sign``) into the aggregator's
     ``count`` cached sign packets; returns theirs.  With error feedback a client's residual
-    advances exactly once, committed after its encode was issued."""
+    advances exactly once, committed after its encode was issued.
+    ``aggregation_config["batched_sign_encode"]`` (opt-in): :func:`_sign_encode_batched`, the
+    same bits."""
     slots = _cached(agg, "_sign_packets", (n, dev), count,
                     lambda count: [codec.SignPacket.alloc(n, dev) for _ in range(count)])[:len(part)]
+    if _config(agg).get("batched_sign_encode", False):
+        _sign_encode_batched(agg, part, slots, n, dev, count)
+        return slots
     for c, slot in zip(part, slots):
         g = torch.from_numpy(np.ascontiguousarray(c.grad)).to(dev)
         if c.C.error_feedback:
@@ -840,7 +886,7 @@ def sign_round(agg, clients, n: int, dev: torch.device) -> torch.Tensor:
     _sign_residuals_ready(clients, n, dev)
     w = None if major else gar._weights(m, np.float32)                # gar.py:37-42 (persisted)
     out = torch.empty(n, dtype=torch.float32, device=dev)
-    agg.sign_groups = 0
+    agg.sign_groups = agg.sign_encode_calls = 0
     for s in range(0, m, group):
         pk = _sign_encode(agg, clients[s:s + group], n, dev, group)
         if major:
@@ -854,6 +900,7 @@ def sign_round(agg, clients, n: int, dev: torch.device) -> torch.Tensor:
 def _sign_encode_resident(agg, clients, n: int, dev: torch.device) -> list:
     """The round's clients encoded into sign packets that all stay resident."""
     _sign_residuals_ready(clients, n, dev)
+    agg.sign_encode_calls = 0
     return _sign_encode(agg, clients, n, dev, len(clients))
 
 

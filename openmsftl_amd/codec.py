@@ -13,6 +13,7 @@
     pkt = unpack(wire_from_host(raw))      # validated host bytes back into a slotted packet
     agg = fold_wire(wires, w)              # decode_accumulate(unpack(wires), w) without the unpack
     pkt, e2 = encode_sign(g, e)            # 1 bit per coordinate and one scale, e2 = a - q
+    pkts, _ = encode_sign_batch(grads)     # M clients in one launch, one read of each gradient
     agg = fold_sign(pkts, w)               # FedAVG of sign packets, the dense fold's bits
     v   = vote_sign(pkts, eta)             # majority vote: -eta / +eta / +0.0 per coordinate
 
@@ -1411,6 +1412,117 @@ def encode_sign(g: torch.Tensor, residual: Optional[torch.Tensor] = None,
                                packet.words.numel(), _vp(packet.hdr), _vp(ws), ws.numel(),
                                _stream(dev)), "fc_sign_encode")
     return packet, residual_out
+
+
+_SIGN_BATCH_WS = {}
+
+
+def sign_jobs(grads: Sequence[torch.Tensor], packets: Sequence[SignPacket],
+              residuals: Optional[Sequence[torch.Tensor]] = None,
+              residuals_out: Optional[Sequence[torch.Tensor]] = None) -> torch.Tensor:
+    """Device array of fc_sign_job for :func:`encode_sign_batch` (build once, reuse while the
+    buffers live)."""
+    m = len(grads)
+    none = [None] * m
+    arr = (L.SignJob * m)(*[
+        L.SignJob(g=g.data_ptr(), res_in=r.data_ptr() if r is not None else 0,
+                  res_out=o.data_ptr() if o is not None else 0, words=p.words.data_ptr(),
+                  hdr=p.hdr.data_ptr(), reserved=0)
+        for g, p, r, o in zip(grads, packets, residuals or none, residuals_out or none)])
+    host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
+    return host.to(grads[0].device)
+
+
+def _disjoint(ranges, what: str) -> None:
+    """``ranges``: (start, bytes, index); ValueError when two of them share a byte."""
+    ranges = sorted(ranges)
+    for (a, la, i), (b, _, j) in zip(ranges, ranges[1:]):
+        if b < a + la:
+            raise ValueError(f"{what}[{i}] and {what}[{j}] overlap")
+
+
+def encode_sign_batch(grads: Sequence[torch.Tensor],
+                      residuals: Optional[Sequence[torch.Tensor]] = None,
+                      residuals_out: Optional[Sequence[torch.Tensor]] = None, *,
+                      want_residuals: Optional[bool] = None,
+                      packets: Optional[Sequence[SignPacket]] = None,
+                      jobs: Optional[torch.Tensor] = None):
+    """:func:`encode_sign` for M equal-length gradients in one launch (two when the new residuals
+    are written; fc_sign_encode_batch): client c's header, words and ``residuals_out[c]`` are, byte
+    for byte, what ``encode_sign(grads[c], residuals[c], residuals_out[c])`` gives.  Returns
+    ``(packets, residuals_out or None)``.
+
+    ``residuals`` is None or one tensor per gradient (zeros are not "no residual" for this codec:
+    a None entry is a ValueError).  The new residuals are written when ``residuals`` or
+    ``residuals_out`` is given, or as ``want_residuals`` says when it is not None; they are
+    allocated when missing.  No ``residuals_out[i]`` may overlap any gradient, residual or other
+    output of the batch, and the packets' storage is distinct (ValueError before any launch).
+    ``jobs``: a prebuilt :func:`sign_jobs` table for these exact buffers."""
+    if not grads:
+        raise ValueError("no gradients")
+    lib = L.load()
+    m = len(grads)
+    if m > 65535:
+        raise ValueError(f"{m} gradients: at most 65535 per call")
+    _require_cuda_f32(grads[0], "g[0]")
+    n, dev = grads[0].numel(), grads[0].device
+    if n < 1:
+        raise ValueError("encode_sign_batch needs n >= 1")
+    want = want_residuals if want_residuals is not None else (residuals is not None or residuals_out is not None)
+    if residuals_out is not None and not want:
+        raise ValueError("residuals_out given with want_residuals=False")
+    for name, ts in (("residuals", residuals), ("residuals_out", residuals_out), ("packets", packets)):
+        if ts is not None and len(ts) != m:
+            raise ValueError(f"{name}: one per gradient")
+    if residuals is not None and any(r is None for r in residuals):
+        raise ValueError("a residual is None: pass residuals=None for a batch without residuals "
+                         "(zeros are not 'no residual' for the sign codec)")
+    if want and residuals_out is None:
+        residuals_out = [torch.empty(n, dtype=torch.float32, device=dev) for _ in range(m)]
+    for name, ts in (("g", grads), ("residual", residuals), ("residual_out", residuals_out)):
+        for i, t in enumerate(ts or ()):
+            _require_cuda_f32(t, f"{name}[{i}]")
+            if t.numel() != n or t.device != dev:
+                raise ValueError(f"{name}[{i}] must have {n} elements on {dev}")
+    nb = 4 * n
+    if want:                 # address ranges on the host: an output against every input and output
+        outs = sorted((o.data_ptr(), i) for i, o in enumerate(residuals_out))
+        _disjoint([(a, nb, i) for a, i in outs], "residuals_out")
+        starts = [a for a, _ in outs]
+        for kind, ts in (("grads", grads), ("residuals", residuals or ())):
+            for j, t in enumerate(ts):
+                p = t.data_ptr()
+                lo = bisect.bisect_right(starts, p - nb)        # first output starting after p - nb
+                if lo < m and starts[lo] < p + nb:
+                    raise ValueError(f"residuals_out[{outs[lo][1]}] overlaps {kind}[{j}]")
+    if packets is None:
+        packets = [SignPacket.alloc(n, dev) for _ in range(m)]
+    need = int(lib.fc_sign_words(n))
+    for i, p in enumerate(packets):
+        if not isinstance(p, SignPacket):
+            raise TypeError("sign packets expected (codec.SignPacket.alloc)")
+        if p.n != n or p.words.device != dev or p.hdr.device != dev:
+            raise ValueError(f"packets[{i}] must have the gradients' length and device")
+        if p.words.dtype != _U32 or p.words.numel() < need or p.words.data_ptr() % 16:
+            raise ValueError("a sign packet's words must be 16-byte aligned int32[fc_sign_words(n)]")
+        if p.hdr.dtype != torch.uint8 or p.hdr.numel() < L.HDR_BYTES or p.hdr.data_ptr() % 8:
+            raise ValueError("a sign packet's header must be 8-byte aligned uint8[96]")
+    _disjoint([(p.words.data_ptr(), 4 * need, i) for i, p in enumerate(packets)], "packets")
+    _disjoint([(p.hdr.data_ptr(), L.HDR_BYTES, i) for i, p in enumerate(packets)], "packets")
+    if jobs is None:
+        jobs = sign_jobs(grads, packets, residuals, residuals_out if want else None)
+    elif (not isinstance(jobs, torch.Tensor) or jobs.device != dev or jobs.dtype != torch.uint8
+          or jobs.numel() < m * ctypes.sizeof(L.SignJob) or jobs.data_ptr() % 8):
+        raise ValueError("jobs must be the uint8 device table codec.sign_jobs made for these buffers")
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(),
+           torch.cuda.current_stream(dev).cuda_stream)        # the clients' tickets: per stream
+    ws = _SIGN_BATCH_WS.get(key)
+    nbytes = int(lib.fc_sign_batch_workspace_bytes(n, m))
+    if ws is None or ws.numel() < nbytes:                     # grown to the largest m seen
+        ws = _SIGN_BATCH_WS[key] = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+    L.check(lib.fc_sign_encode_batch(_vp(jobs), m, n, int(residuals is not None), int(bool(want)),
+                                     _vp(ws), ws.numel(), _stream(dev)), "fc_sign_encode_batch")
+    return list(packets), (list(residuals_out) if want else None)
 
 
 def decode_sign(packet: SignPacket, out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -17,6 +17,10 @@
 //                 component (four per 256 elements: one per 64 elements); lanes 0..7 each assemble
 //                 one whole word from byte l of the four ballots (spread4) and store it; e' goes out
 //                 as one 16-B store per lane.  4N (8N) read, N/8 (+ 4N) written.
+// Batched encode (fc_sign_encode_batch), m clients per launch, client = blockIdx.y:
+//   k_sign_encode1_batch  k_sign_norm's grid, loop and sum per client with k_sign_pack's ballots
+//                 in the loop: header and words from ONE read, 4N (8N) + N/8 per client.
+//   k_sign_resid_batch    only when e' is wanted: 4N (8N) read, 4N written per client.
 // Decode: k_sign_decode, one 16-B store per lane.
 // Fold and vote, three forms of bringing a client's words to the lanes (fc_sign_fold_form; the
 //   results are the same bits, tools/sign_bench.py measures them side by side):
@@ -35,7 +39,9 @@
 namespace fc {
 
 constexpr int kSignNormGrid = 1024;            // fixed: the fp64 sum order depends on it
+constexpr size_t kSignWsBytes = 64 + 8 * (size_t)kSignNormGrid;   // a ticket (own line) and the partials
 constexpr int kSignNormUnroll = 2;             // 16-B loads in flight per thread (k_qsgd_norm's)
+constexpr int kSignResidGrid = 8192;           // k_sign_resid_batch workgroups per client at most (k_sign_pack's)
 constexpr int FC_SIGN_PACK_GRID = 8192;        // k_sign_pack / k_sign_decode workgroups at most
 constexpr int kSignBatch = 256;                // clients staged in LDS per round of fold / vote
 constexpr int kSignGroups = 8;                 // 64-coordinate groups per wave (512 coordinates)
@@ -110,6 +116,164 @@ __global__ __launch_bounds__(kBlock) void k_sign_norm(const float* __restrict__ 
     hdr->chunk = 0; hdr->format = FC_FMT_SIGN; hdr->key_mode = 0;
     hdr->reserved[0] = hdr->reserved[1] = hdr->reserved[2] = 0;
     *ticket = 0;                                                  // for the next encode
+  }
+}
+
+// ---- the batched encode (fc_sign_encode_batch): client = blockIdx.y --------------------------
+// float4 load of [e0, e0 + 4) of a job's array with zero fill past n: load4 through the GLOBAL
+// address space (the pointer comes out of the job table).
+__device__ __forceinline__ float4 sign_load4(const FC_G float* p, uint64_t e0, uint64_t n) {
+  if (e0 + 4 <= n) {
+    const fc_f4v v = __builtin_nontemporal_load((fc_gf4v*)(p + e0));
+    return make_float4(v.x, v.y, v.z, v.w);
+  }
+  float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (e0 + 0 < n) r.x = p[e0 + 0];
+  if (e0 + 1 < n) r.y = p[e0 + 1];
+  if (e0 + 2 < n) r.z = p[e0 + 2];
+  return r;
+}
+__device__ __forceinline__ float4 sign_add4(float4 a, float4 r) {
+  return make_float4(__fadd_rn(a.x, r.x), __fadd_rn(a.y, r.y), __fadd_rn(a.z, r.z), __fadd_rn(a.w, r.w));
+}
+
+// The end of k_sign_norm for the batched kernel, statement for statement: every thread's fp64 sum
+// acc to the wave, the workgroup, partial[blockIdx.x]; the last-arriving workgroup of the gridDim.x
+// that count into *ticket adds the partials in index order, writes the header and clears the
+// ticket.  (A copy: called from k_sign_norm too, hipcc allocated that kernel's registers
+// differently, and fc_sign_encode's generated code stays as it was.)
+__device__ __forceinline__ void sign_norm_finish(double acc, uint64_t n, double* partial,
+                                                 uint32_t* ticket, fc_packet_hdr* hdr,
+                                                 double* s_red, uint32_t* s_flag,
+                                                 int tid, int lane, int w) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  if (lane == 0) s_red[w] = acc;
+  __syncthreads();
+  if (tid == 0) {
+    double b = 0.0;
+    for (int i = 0; i < kBlock / 64; ++i) b += s_red[i];
+    st_agent(reinterpret_cast<uint64_t*>(&partial[blockIdx.x]), (uint64_t)__double_as_longlong(b));
+  }
+  if (!last_block_arrive_sc1(ticket, gridDim.x, s_flag)) return;
+  // ---- last workgroup: fixed-order sum of the partials, header --------------------------
+  double t = 0.0;
+  for (uint32_t i = (uint32_t)tid; i < gridDim.x; i += kBlock)
+    t += __longlong_as_double((long long)ld_agent(reinterpret_cast<const uint64_t*>(&partial[i])));
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+  __syncthreads();
+  if (lane == 0) s_red[w] = t;
+  __syncthreads();
+  if (tid == 0) {
+    double sum = 0.0;
+    for (int i = 0; i < kBlock / 64; ++i) sum += s_red[i];
+    const float s = (float)(sum / (double)n);
+    hdr->thresh = 0; hdr->lower = 0;
+    hdr->n = (uint32_t)n; hdr->k = (uint32_t)n; hdr->n_entries = (uint32_t)n;
+    hdr->index_bits = 0; hdr->codec = FC_CODEC_SIGN; hdr->status = FC_STATUS_OK;
+    hdr->n_definite = 0; hdr->n_cand = 0;
+    hdr->seed = 0; hdr->offset = 0; hdr->p = (double)s;
+    hdr->chunk = 0; hdr->format = FC_FMT_SIGN; hdr->key_mode = 0;
+    hdr->reserved[0] = hdr->reserved[1] = hdr->reserved[2] = 0;
+    *ticket = 0;                                                  // for the next encode
+  }
+}
+
+// One read for the header AND the words: k_sign_norm's grid and grid-stride loop with k_sign_pack's
+// ballots inside it.  In k_sign_norm wave w of workgroup b loads at step j the 64 consecutive
+// float4 from 256 b + 64 w + j * stride, stride = 256 * gridDim.x a multiple of 64: elements
+// 256 t .. 256 t + 255 of tile t = 4 b + w + 4 gridDim.x j, lane l holding 4 l .. 4 l + 3, which is
+// one k_sign_pack tile.  So the loop runs over the wave's tiles t < ceil(n / 256) (wave-uniform:
+// every ballot sees 64 lanes), a lane adds its float4 exactly when k_sign_norm's thread would
+// (q < n / 4, ascending j, .x .y .z .w; workgroup 0's tail scalars last), and the rest of the sum
+// is sign_norm_finish: s has k_sign_norm's bits.  The lane that owns float4 index n / 4 loads the
+// n % 4 tail elements for their bits alone.  Tiles below n / 256 are whole: two of them in flight
+// per wave with no predicate, as k_sign_norm's unrolled loop.
+template <bool RES>
+__global__ __launch_bounds__(kBlock) void k_sign_encode1_batch(const fc_sign_job* __restrict__ jobs,
+                                                               uint64_t n, uint64_t n_words, char* ws) {
+  __shared__ double s_red[kBlock / 64];
+  __shared__ uint32_t s_flag;
+  const FC_G fc_sign_job* job = (const FC_G fc_sign_job*)jobs + blockIdx.y;
+  const FC_G float* g = (const FC_G float*)job->g;
+  const FC_G float* e = (const FC_G float*)job->res_in;
+  FC_G uint32_t* words = (FC_G uint32_t*)job->words;
+  char* wc = ws + (size_t)blockIdx.y * kSignWsBytes;
+  const int tid = threadIdx.x;
+  const uint32_t lane = (uint32_t)lane_id();
+  const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane(tid >> 6);
+  const uint64_t n4 = n / 4, whole = n / 256, tiles = (n + 255) / 256;
+  const uint64_t tstep = (uint64_t)gridDim.x * kWaves;
+  double acc = 0.0;
+  auto sum4 = [&](float4 v) {
+    acc += (double)__builtin_fabsf(v.x); acc += (double)__builtin_fabsf(v.y);
+    acc += (double)__builtin_fabsf(v.z); acc += (double)__builtin_fabsf(v.w);
+  };
+  auto put = [&](uint64_t t, float4 a, bool all) {       // k_sign_pack's ballots and word stores
+    const uint64_t m0 = __ballot(sign_bit(a.x)), m1 = __ballot(sign_bit(a.y));
+    const uint64_t m2 = __ballot(sign_bit(a.z)), m3 = __ballot(sign_bit(a.w));
+    if (lane < 8u && (all || t * 8 + lane < n_words)) {
+      const uint32_t sh = 8u * lane;
+      words[t * 8 + lane] = spread4((uint32_t)(m0 >> sh)) | (spread4((uint32_t)(m1 >> sh)) << 1) |
+                            (spread4((uint32_t)(m2 >> sh)) << 2) | (spread4((uint32_t)(m3 >> sh)) << 3);
+    }
+  };
+  uint64_t t = (uint64_t)blockIdx.x * kWaves + w;
+  for (; t + tstep < whole; t += 2 * tstep) {
+    const uint64_t e0 = t * 256 + 4 * lane, e1 = e0 + tstep * 256;
+    float4 a0 = load4_full((const float*)(g + e0)), a1 = load4_full((const float*)(g + e1));
+    if (RES) {
+      const float4 r0 = load4_full((const float*)(e + e0)), r1 = load4_full((const float*)(e + e1));
+      a0 = sign_add4(a0, r0); a1 = sign_add4(a1, r1);
+    }
+    sum4(a0); put(t, a0, true);
+    sum4(a1); put(t + tstep, a1, true);
+  }
+  for (; t < tiles; t += tstep) {
+    const uint64_t e0 = t * 256 + 4 * lane;
+    float4 a = sign_load4(g, e0, n);
+    if (RES) a = sign_add4(a, sign_load4(e, e0, n));
+    if (t * 64 + lane < n4) sum4(a);
+    put(t, a, false);
+  }
+  if (blockIdx.x == 0 && tid < (int)(n - 4 * n4)) {            // tail (< 4 elements), added last
+    float x = g[4 * n4 + tid];
+    if (RES) x = __fadd_rn(x, e[4 * n4 + tid]);
+    acc += (double)__builtin_fabsf(x);
+  }
+  sign_norm_finish(acc, n, reinterpret_cast<double*>(wc + 64), reinterpret_cast<uint32_t*>(wc),
+                   job->hdr, s_red, &s_flag, tid, (int)lane, tid >> 6);
+}
+
+// The second launch when e' is wanted: s from the client's own header, e' = fl32(a - (+-s)) as
+// k_sign_pack<., true> computes it, one non-temporal 16-B store per float4, in k_sign_pack's
+// geometry (a float4 per thread and step, at most 8192 workgroups per client).
+template <bool RES>
+__global__ __launch_bounds__(kBlock) void k_sign_resid_batch(const fc_sign_job* __restrict__ jobs,
+                                                             uint64_t n) {
+  const FC_G fc_sign_job* job = (const FC_G fc_sign_job*)jobs + blockIdx.y;
+  const FC_G float* g = (const FC_G float*)job->g;
+  const FC_G float* e = (const FC_G float*)job->res_in;
+  FC_G float* eout = (FC_G float*)job->res_out;
+  const float s = (float)((const FC_G fc_packet_hdr*)job->hdr)->p;
+  const int tid = threadIdx.x;
+  const uint64_t n4 = n / 4, stride = (uint64_t)gridDim.x * kBlock;
+  auto resid = [&](float x) { return __fsub_rn(x, sign_bit(x) ? -s : s); };
+  auto store = [&](uint64_t q, float4 a) {
+    __builtin_nontemporal_store(fc_f4v{resid(a.x), resid(a.y), resid(a.z), resid(a.w)},
+                                (FC_G fc_f4v*)(eout + 4 * q));
+  };
+  uint64_t q = (uint64_t)blockIdx.x * kBlock + tid;
+  for (; q < n4; q += stride) {
+    float4 a = load4_full((const float*)(g + 4 * q));
+    if (RES) a = sign_add4(a, load4_full((const float*)(e + 4 * q)));
+    store(q, a);
+  }
+  if (blockIdx.x == 0 && tid < (int)(n - 4 * n4)) {            // tail (< 4 elements)
+    float x = g[4 * n4 + tid];
+    if (RES) x = __fadd_rn(x, e[4 * n4 + tid]);
+    eout[4 * n4 + tid] = resid(x);
   }
 }
 
@@ -400,7 +564,11 @@ uint64_t fc_sign_words(uint64_t n) { return sign_words(n); }
 
 size_t fc_sign_workspace_bytes(uint64_t n) {
   (void)n;
-  return 64 + 8 * (size_t)kSignNormGrid;
+  return kSignWsBytes;
+}
+
+size_t fc_sign_batch_workspace_bytes(uint64_t n, int m) {
+  return (size_t)(m < 1 ? 1 : m) * fc_sign_workspace_bytes(n);
 }
 
 int fc_sign_wire_validate(const void* host_bytes, size_t len, uint64_t n_expected) {
@@ -448,6 +616,42 @@ int fc_sign_encode(const float* g, const float* res_in, float* res_out, uint64_t
   else if (res_out) hipLaunchKernelGGL((k_sign_pack<false, true>), grid, blk, 0, s, g, res_in, res_out, n, hdr, words, nw);
   else hipLaunchKernelGGL((k_sign_pack<false, false>), grid, blk, 0, s, g, res_in, res_out, n, hdr, words, nw);
   FC_LAUNCHED("k_sign_pack");
+  return FC_OK;
+}
+
+int fc_sign_encode_batch(const fc_sign_job* jobs_dev, int m, uint64_t n, int has_res_in,
+                         int has_res_out, void* ws, size_t ws_bytes, fc_stream_t stream) {
+  FC_CHECK(jobs_dev && ws, "NULL argument");
+  FC_CHECK(m >= 1 && m <= 65535, "m=%d outside [1, 65535]", m);
+  FC_CHECK(n >= 1 && n <= 0xffffffffull, "n=%llu outside [1, 2^32-1]", (unsigned long long)n);
+  FC_CHECK(((uintptr_t)jobs_dev & 7) == 0 && ((uintptr_t)ws & 7) == 0,
+           "the job table and the workspace must be 8-byte aligned");
+  if (ws_bytes < fc_sign_batch_workspace_bytes(n, m))
+    return fail(FC_ERR_WORKSPACE, "workspace %zu B < %zu B needed", ws_bytes,
+                fc_sign_batch_workspace_bytes(n, m));
+  hipStream_t s = (hipStream_t)stream;
+  char* w = static_cast<char*>(ws);
+  uint64_t ng = (n / 4 + kBlock - 1) / kBlock;                 // fc_sign_encode's: fixed for a given n
+  if (ng < 1) ng = 1;
+  if (ng > (uint64_t)kSignNormGrid) ng = kSignNormGrid;
+  const uint64_t nw = fc_sign_words(n);
+  const dim3 blk(kBlock);
+  {
+    TimedLaunch t(FC_TIME_SAMPLE, s);
+    const dim3 grid((uint32_t)ng, (uint32_t)m);
+    if (has_res_in) hipLaunchKernelGGL(k_sign_encode1_batch<true>, grid, blk, 0, s, jobs_dev, n, nw, w);
+    else hipLaunchKernelGGL(k_sign_encode1_batch<false>, grid, blk, 0, s, jobs_dev, n, nw, w);
+    FC_LAUNCHED("k_sign_encode1_batch");
+  }
+  if (!has_res_out) return FC_OK;
+  uint64_t nr = (n / 4 + kBlock - 1) / kBlock;
+  if (nr < 1) nr = 1;
+  if (nr > (uint64_t)kSignResidGrid) nr = kSignResidGrid;
+  TimedLaunch t(FC_TIME_COMPACT, s);
+  const dim3 grid((uint32_t)nr, (uint32_t)m);
+  if (has_res_in) hipLaunchKernelGGL(k_sign_resid_batch<true>, grid, blk, 0, s, jobs_dev, n);
+  else hipLaunchKernelGGL(k_sign_resid_batch<false>, grid, blk, 0, s, jobs_dev, n);
+  FC_LAUNCHED("k_sign_resid_batch");
   return FC_OK;
 }
 

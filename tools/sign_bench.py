@@ -2,6 +2,7 @@
 
     python tools/sign_bench.py [--shapes 128x16777216,32x134217728] [--agg-shapes 32x25500000]
                                [--f 0.1] [--out FILE]
+    python tools/sign_bench.py --batch [--batch-shapes 128x16777216,32x134217728] [--out FILE]
 
 Per shape M x N (HIP events, the forms alternating over the rounds after a warm-up, the figure the
 median round with min-max beside it), one JSON line:
@@ -20,6 +21,13 @@ median round with min-max beside it), one JSON line:
 Aggregator part (--agg-shapes), one JSON line per shape:
 (e) wall time of one round, host gradients (or payloads) in, host aggregate out, through "sign",
     "dense-fold" ("sign_packets": False) and "wire-sign" (the payloads made beforehand)
+Batched encode (--batch: this part alone), one JSON line per shape M x N:
+(f) M lone encodes against ONE codec.encode_sign_batch with a prebuilt job table, device-resident
+    gradients, in three forms: without residuals, with res_in only (the lone side calls
+    fc_sign_encode with a NULL res_out: codec.encode_sign always writes e'), with res_in and
+    res_out.  Whole-call times, the six alternating in one process; each form's byte model (lone
+    8N / 16N / 20N + N/8, batched 4N / 8N / 20N + N/8 per client) as a fraction of 8 TB/s, and the
+    lone two-pass time per client; the first and last client's bytes are compared once per form.
 Needs a GPU: no fallback.
 """
 import argparse
@@ -44,6 +52,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--agg-rounds", type=int, default=2)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--batch", action="store_true", help="the batched-encode part alone")
+    ap.add_argument("--batch-shapes", default="128x16777216,32x134217728")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -92,6 +102,72 @@ def main():
             finally:
                 lib.fc_sign_fold_form(-1)
         return run
+
+    # ---- (f) the batched encode ----
+    for shape in [s for s in a.batch_shapes.split(",") if s and a.batch]:
+        m, n = (int(x) for x in shape.split("x"))
+        gen = torch.Generator(device=dev).manual_seed(n % 1000 + 17)
+        gs = [torch.randn(n, device=dev, generator=gen) for _ in range(m)]
+        es = [torch.randn(n, device=dev, generator=gen) * 0.5 for _ in range(m)]
+        outs = [torch.empty(n, device=dev) for _ in range(m)]
+        lone_pk = [codec.SignPacket.alloc(n, dev) for _ in range(m)]
+        bat_pk = [codec.SignPacket.alloc(n, dev) for _ in range(m)]
+        jobs = {"plain": codec.sign_jobs(gs, bat_pk), "res_in": codec.sign_jobs(gs, bat_pk, es),
+                "ef": codec.sign_jobs(gs, bat_pk, es, outs)}
+        codec.encode_sign(gs[0], packet=lone_pk[0])                      # makes the lone workspace
+        ws = codec._SIGN_WS[(dev.index, torch.cuda.current_stream(dev).cuda_stream)]
+
+        def lone_plain():
+            for g, p in zip(gs, lone_pk):
+                codec.encode_sign(g, packet=p)
+
+        def lone_res_in():
+            st = codec._stream(dev)
+            for g, e, p in zip(gs, es, lone_pk):
+                L.check(lib.fc_sign_encode(codec._vp(g), codec._vp(e), None, n, codec._vp(p.words),
+                                           p.words.numel(), codec._vp(p.hdr), codec._vp(ws), ws.numel(), st),
+                        "fc_sign_encode")
+
+        def lone_ef():
+            for g, e, o, p in zip(gs, es, outs, lone_pk):
+                codec.encode_sign(g, e, residual_out=o, packet=p)
+
+        forms = {"lone_plain": lone_plain,
+                 "batch_plain": lambda: codec.encode_sign_batch(gs, packets=bat_pk, jobs=jobs["plain"]),
+                 "lone_res_in": lone_res_in,
+                 "batch_res_in": lambda: codec.encode_sign_batch(gs, es, want_residuals=False, packets=bat_pk,
+                                                                 jobs=jobs["res_in"]),
+                 "lone_ef": lone_ef,
+                 "batch_ef": lambda: codec.encode_sign_batch(gs, es, outs, packets=bat_pk, jobs=jobs["ef"])}
+        same = {}
+        for form in ("plain", "res_in", "ef"):
+            keep = []
+            for side in ("lone", "batch"):
+                for p in lone_pk + bat_pk:
+                    p.words.fill_(-1)
+                outs[0].fill_(0), outs[-1].fill_(0)
+                forms[f"{side}_{form}"]()
+                pk = lone_pk if side == "lone" else bat_pk
+                keep.append([t.cpu().numpy().tobytes() for i in (0, m - 1)
+                             for t in (pk[i].hdr, pk[i].words, outs[i])])
+            same[form] = keep[0] == keep[1]
+        t = alternate(forms, max(a.rounds, 5))
+        lone_b = {"plain": 8 * n + n / 8, "res_in": 16 * n + n / 8, "ef": 20 * n + n / 8}
+        bat_b = {"plain": 4 * n + n / 8, "res_in": 8 * n + n / 8, "ef": 20 * n + n / 8}
+        emit({"bench": "sign_batch_bench", "M": m, "N": n, "rounds": max(a.rounds, 5),
+              "us": {k_: v[0] for k_, v in t.items()}, "minmax": {k_: v[1] for k_, v in t.items()},
+              "batch_over_lone": {f: round(t[f"batch_{f}"][0] / t[f"lone_{f}"][0], 3) for f in lone_b},
+              "lone_us_per_client": {f: round(t[f"lone_{f}"][0] / m, 1) for f in lone_b},
+              "batch_us_per_client": {f: round(t[f"batch_{f}"][0] / m, 1) for f in lone_b},
+              "lone_model_frac_of_8TBs": {f: round(m * b / PEAK * 1e6 / t[f"lone_{f}"][0], 3)
+                                          for f, b in lone_b.items()},
+              "batch_model_frac_of_8TBs": {f: round(m * b / PEAK * 1e6 / t[f"batch_{f}"][0], 3)
+                                           for f, b in bat_b.items()},
+              "batch_equals_lone_bytes": same})
+        del gs, es, outs, lone_pk, bat_pk, jobs
+        torch.cuda.empty_cache()
+    if a.batch:
+        return
 
     for shape in [s for s in a.shapes.split(",") if s]:
         m, n = (int(x) for x in shape.split("x"))
