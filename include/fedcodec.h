@@ -519,6 +519,48 @@ int fc_qsgd_decode(const fc_packet_view* pkt, uint64_t n, float* out, fc_stream_
 int fc_qsgd_decode_accumulate(const fc_packet_view* views_dev, int m, uint64_t n, float* out,
                               int continue_sum, fc_stream_t stream);
 
+/* ---- QSGD with error feedback and the QSGD packet's wire form (fc_qsgd.hip, fc_qsgd_host.h) ----
+ * The quantiser above divides by tau, so E[q] = g / tau: a contraction, the form EF-signSGD
+ * (Karimireddy, Rebjock, Stich, Jaggi, ICML 2019) takes error feedback for.  For a float32 gradient
+ * g[n], n >= 1, and an optional float32 residual e[n]:
+ *   a[t] = fl32(g[t] + e[t]), one IEEE add (so -0.0 + +0.0 = +0.0); a[t] = g[t] without res_in
+ *   header (all 96 bytes) and codes: byte for byte what fc_qsgd_encode writes for an array holding
+ *          a: the fp64 norm summed in the same fixed order (same grid, same per-thread order, same
+ *          tail), the same Philox map, the same choice between the fp32 and the fp64 form of the
+ *          level, the clamp to s and NaN -> level 0.  Nothing is special-cased
+ *   q[t] = what fc_qsgd_decode writes for that packet: (float)(+-(norm / (s tau)) * l), an fp64
+ *          product and one rounding
+ *   e'[t] = fl32(a[t] - q[t]), one IEEE subtract, into res_out (a non-finite gradient poisons it
+ *          exactly as this arithmetic says)
+ * fc_qsgd_encode_ef: g, res_in (NULL: none), res_out (NULL: not wanted) and codes all 16-B aligned;
+ *   res_out may not overlap g or res_in; code_words >= fc_qsgd_code_words(n, bits).  With both
+ *   residual pointers NULL the call is fc_qsgd_encode.  Two launches (the norm pass, whose last
+ *   arriver writes the header, and the quantise pass), neither waits in-kernel for another
+ *   workgroup: no fc_fused_order_* handling.  ws: fc_qsgd_workspace_bytes(), fc_qsgd_encode's
+ *   contract.  Bytes with both residuals: 16N read in two passes over g and e, 4N + N W / 8 written.
+ *   Argument errors (NULL, n, bits, alignment, overlap, code_words: FC_ERR_ARG; a short workspace:
+ *   FC_ERR_WORKSPACE) are reported before the GPU is touched.
+ * Wire form (openmsftl_amd/csrc/fc_qsgd_host.h): a 128-byte header (uint32 magic "FCQ1", uint32
+ *   version 1, uint64 total_bytes, 16 zero bytes, the canonical fc_packet_hdr) and the
+ *   fc_qsgd_code_words(n, bits) uint32 of codes padded with zero words to a multiple of 4.
+ *   fc_qsgd_wire_bytes: its size, a function of n and bits alone; 0 for bits outside [1, 14].
+ * fc_qsgd_wire_validate: HOST bytes, no GPU.  FC_OK, or FC_ERR_ARG with the reason in
+ *   fc_last_error(), reading nothing past len: NULL; shorter than the header; a wrong magic or
+ *   version; total_bytes != len; the reserved bytes; n = 0 or n != n_expected (unless that is 0);
+ *   codec or format other than QSGD; k (bits) outside [1, 14]; n_entries != n; a status other than
+ *   OK; key_mode other than FC_KEY_PHILOX; a field that must be zero (thresh, lower, index_bits,
+ *   n_definite, n_cand, chunk, reserved); a negative norm p (NaN excepted; p is any other double);
+ *   len != fc_qsgd_wire_bytes(n, bits); a code whose level exceeds s = 2^bits (the field is W - 1
+ *   bits wide; the encoder never writes one); a non-zero code at or past n inside the last group;
+ *   a non-zero pad word.  seed and offset may be anything.  fc_wire_validate and
+ *   fc_sign_wire_validate reject these bytes by their magic. */
+int fc_qsgd_encode_ef(const float* g, const float* res_in /* NULL: none */,
+                      float* res_out /* NULL: not wanted */, uint64_t n, int bits,
+                      uint64_t seed, uint64_t offset, uint32_t* codes, uint64_t code_words,
+                      fc_packet_hdr* hdr, void* ws, size_t ws_bytes, fc_stream_t stream);
+uint64_t fc_qsgd_wire_bytes(uint64_t n, int bits);
+int fc_qsgd_wire_validate(const void* host_bytes, size_t len, uint64_t n_expected /* 0 = any */);
+
 /* ---- scaled sign with error feedback, its FedAVG fold and the majority vote (fc_sign.hip) ----
  * The 1-bit codec (EF-signSGD: Karimireddy, Rebjock, Stich, Jaggi, ICML 2019; opt-in, no reference
  * counterpart) and the cheapest coordinate-wise robust rule over its packets (signSGD with

@@ -97,9 +97,17 @@ class SignWireHdr(ctypes.Structure):
                 ("total_bytes", ctypes.c_uint64), ("zero", ctypes.c_uint32 * 4), ("pkt", PacketHdr)]
 
 
+class QsgdWireHdr(ctypes.Structure):
+    """fc_qsgd_wire_hdr: the first 128 bytes of a QSGD packet's wire form."""
+    _fields_ = [("magic", ctypes.c_uint32), ("version", ctypes.c_uint32),
+                ("total_bytes", ctypes.c_uint64), ("zero", ctypes.c_uint32 * 4), ("pkt", PacketHdr)]
+
+
 SIGN_MAGIC = 0x31534346            # "FCS1"
+QSGD_MAGIC = 0x31514346            # "FCQ1"
 WIRE_HDR_BYTES = 128
 assert ctypes.sizeof(SignWireHdr) == WIRE_HDR_BYTES
+assert ctypes.sizeof(QsgdWireHdr) == WIRE_HDR_BYTES
 assert ctypes.sizeof(WireJob) == 16
 assert ctypes.sizeof(WireHdr) == WIRE_HDR_BYTES
 assert ctypes.sizeof(PermState) == 2520
@@ -162,6 +170,9 @@ SIGNATURES = {
     "fc_qsgd_encode": (_i32, [_vp, _u64, _i32, _u64, _u64, _vp, _u64, _vp, _vp, _sz, _vp]),
     "fc_qsgd_decode": (_i32, [ctypes.POINTER(PacketView), _u64, _vp, _vp]),
     "fc_qsgd_decode_accumulate": (_i32, [_vp, _i32, _u64, _vp, _i32, _vp]),
+    "fc_qsgd_encode_ef": (_i32, [_vp, _vp, _vp, _u64, _i32, _u64, _u64, _vp, _u64, _vp, _vp, _sz, _vp]),
+    "fc_qsgd_wire_bytes": (_u64, [_u64, _i32]),
+    "fc_qsgd_wire_validate": (_i32, [_vp, _sz, _u64]),
     "fc_sign_words": (_u64, [_u64]),
     "fc_sign_workspace_bytes": (_sz, [_u64]),
     "fc_sign_encode": (_i32, [_vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _sz, _vp]),

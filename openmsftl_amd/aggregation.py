@@ -34,6 +34,11 @@ hierarchies, one device, float32 or no GAR weights, 1-D float32 gradients (paylo
                   outside the conditions goes on down this          ``sign_packets:       sized by the budget;
                   table) or sign_majority (it is refused,           False`` (fed_avg)     sign_majority: all M
                   unweighted) (:func:`sign_route`)
+"qsgd"            packet round, n > 0, fed_avg, all clients the     ``qsgd_packets``      a group of QSGD packets (N W / 8
+                  drop-in native 'qsgd' with num_bits in [1, 14]                          bytes each, W = 4 / 8 / 16) sized by
+                  (they may differ in bits), with or without error                        the budget, one gradient in flight
+                  feedback (:func:`qsgd_route`; a round outside the
+                  conditions goes on down this table)
 "ef-batch"        packet round, fed_avg, all clients the drop-in    ``batched_error_      groups of <= 64 gradients, residuals
                   'top' with error feedback at one fraction with    feedback``            and packets (:func:`ef_batch_group`)
                   0 < k < n (:func:`ef_batch_k`)
@@ -56,6 +61,8 @@ hierarchies, one device, float32 or no GAR weights, 1-D float32 gradients (paylo
                   groups or sign_majority ("sign")                                        sign_majority: all M
 "wire-sign-gram"  the same, M <= 128, the schemes of "sign-gram"    ``sign_geometry``     as "sign-gram"
 "wire-sign-trim"  the same, M <= 128, the schemes of "sign-trim"    ``sign_trim``         as "sign-trim"
+"wire-qsgd"       packet round of QSGD payloads; fed_avg in         -                     a group's QSGD packets
+                  groups ("qsgd")                                                         (:func:`wire_fold_groups`)
 ================  ================================================  ====================  ====================================
 
 * ``batched_sign_encode`` (opt-in) names no route: on "sign", "sign-gram" and "sign-trim" it uploads
@@ -463,6 +470,7 @@ _sign_no = _needs("the sign route (sign packets: fed_avg / sign_majority)")
 _sign_gram_no = _needs("the sign-gram route (sign_geometry)")
 _sign_trim_no = _needs("the sign-trim route (sign_trim)")
 _wire_no = _needs("aggregate_wire")
+_qsgd_no = _needs("the qsgd route (qsgd_packets)")
 
 
 def _config(agg) -> dict:
@@ -1026,10 +1034,127 @@ def sign_wire_round(agg, hosts, n: int, dev: torch.device) -> torch.Tensor:
     return out
 
 
+# ---- rounds of QSGD clients: only their N W / 8-byte packets resident -------------------------
+def _qsgd_bits(C) -> Optional[int]:
+    """num_bits of a client that compresses with the native 'qsgd' at an integer number of bits in
+    [1, 14], else None."""
+    if getattr(C, "compression_function", None) != "qsgd" or getattr(C, "qsgd", None) != "native":
+        return None
+    b = getattr(C, "num_bits", None)
+    if isinstance(b, bool) or not isinstance(b, (int, np.integer)) or not 1 <= b <= 14:
+        return None
+    return int(b)
+
+
+def qsgd_packet_bytes(n: int, bits: int) -> int:
+    """Device bytes of one resident QSGD packet: its codes and header, rounded up to 256."""
+    return codec.slab_bytes(4 * int(L.load().fc_qsgd_code_words(n, bits)) + L.HDR_BYTES)
+
+
+def qsgd_route(agg, clients) -> bool:
+    """Does this round take the opt-in "qsgd" route?  True when
+    ``aggregation_config["qsgd_packets"]`` is set, every client is the drop-in ``Compression`` with
+    the native 'qsgd' at ``num_bits`` in [1, 14] (they may differ in bits, and in error feedback),
+    the gradients are 1-D float32 of one length n > 0, there are no hierarchies, one device is used
+    and the GAR is the device ``FedAvg`` with float32 or no weights and without
+    ``pc_analysis: "gram"``.  A round outside these conditions answers False (the generic routes
+    take it, as they take a ``fed_avg`` round of 'sign' clients).  Touches no GPU."""
+    if not _config(agg).get("qsgd_packets", False) or not clients:
+        return False
+    if type(getattr(agg, "gar", None)) is not FedAvg or gram_wanted(agg):
+        return False
+    try:
+        _drop_in(clients, _refused)
+        if any(_qsgd_bits(c.C) is None for c in clients):
+            _refused("every client to compress with the native 'qsgd' at 1..14 bits")
+        _sign_conditions(agg, clients, _refused)      # the packet-round conditions, n > 0
+    except _Refused:
+        return False
+    return True
+
+
+def _qsgd_fold_group(agg, n: int, m: int, per_packet: int, dev: torch.device) -> int:
+    """Packets per fold group: what fits beside the aggregate and the gradient in flight."""
+    return int(max(1, min(m, 65535, (_budget(agg, dev) - 8 * n) // per_packet)))
+
+
+def qsgd_round(agg, clients, n: int, dev: torch.device) -> torch.Tensor:
+    """One round on the "qsgd" route.  The clients are uploaded and encoded one at a time into the
+    aggregator's cached packets (``codec.encode_qsgd``: fc_qsgd_encode_ef with the client's residual
+    buffers under error feedback, fc_qsgd_encode otherwise; each client's Philox offset is taken
+    once and its residual is committed after its encode was issued), so only their codes stay
+    resident.  They are folded in row order in groups sized by the budget, continuing the sum
+    (``codec.decode_accumulate_qsgd``: the "dense-fold" route's bits); ``agg.qsgd_groups`` counts
+    the groups."""
+    gar, m = agg.gar, len(clients)
+    bits = [_qsgd_bits(c.C) for c in clients]
+    per = qsgd_packet_bytes(n, max(bits))              # a slot takes any client of the round
+    group = _qsgd_fold_group(agg, n, m, per, dev)
+    _sign_residuals_ready(clients, n, dev)             # every residual checked before one advances
+    w = gar._weights(m, np.float32)                                   # gar.py:37-42 (persisted)
+    out = torch.empty(n, dtype=torch.float32, device=dev)
+    slots = _cached(agg, "_qsgd_packets", (n, per, dev), group,
+                    lambda count: [codec.QsgdPacket.alloc(n, max(bits), dev) for _ in range(count)])
+    agg.qsgd_groups = 0
+    for s in range(0, m, group):
+        pk = slots[:len(clients[s:s + group])]
+        for c, b, slot in zip(clients[s:s + group], bits[s:s + group], pk):
+            g = torch.from_numpy(np.ascontiguousarray(c.grad)).to(dev)
+            C = c.C
+            slot.bits = b
+            if C.error_feedback:
+                res, spare = C._ef_buffers(n, dev)
+                _, new = codec.encode_qsgd(g, b, seed=C.seed, offset=C._next_offset(), packet=slot,
+                                           residual=res, residual_out=spare)
+                C._ef_commit(res, new, True)
+            else:
+                codec.encode_qsgd(g, b, seed=C.seed, offset=C._next_offset(), packet=slot)
+        codec.decode_accumulate_qsgd(pk, [float(x) for x in w[s:s + len(pk)]], out=out,
+                                     continue_sum=s > 0)
+        agg.qsgd_groups += 1
+    return out
+
+
+def qsgd_wire_round(agg, hosts, n: int, dev: torch.device) -> torch.Tensor:
+    """aggregate_wire's round of validated QSGD payloads (``hosts``: what ``codec._qsgd_check``
+    returned for each): uploaded group by group into one cached device slab
+    (:func:`wire_fold_groups`) and folded in row order, continuing the sum: the "qsgd" route's
+    bits."""
+    gar, m = agg.gar, len(hosts)
+    groups = wire_fold_groups([a.size for a, _ in hosts], n, _budget(agg, dev))
+    wts = gar._weights(m, np.float32)                                 # gar.py:37-42 (persisted)
+    out = torch.empty(n, dtype=torch.float32, device=dev)
+    agg.qsgd_groups = 0
+    for gi, g in enumerate(groups):
+        pk = _slab_upload(agg, "_qsgd_wire", codec._qsgd_upload, hosts[g.start:g.stop], dev)
+        codec.decode_accumulate_qsgd(pk, [float(x) for x in wts[g.start:g.stop]], out=out,
+                                     continue_sum=gi > 0)
+        agg.qsgd_groups += 1
+    return out
+
+
+def _aggregate_wire_qsgd(agg, payloads, kinds, n: Optional[int]) -> None:
+    """aggregate_wire for a round that holds QSGD payloads ("wire-qsgd"): every refusal that needs
+    no GPU, the host validation, then :func:`qsgd_wire_round`."""
+    no = _wire_no
+    if not all(kinds):
+        no("payloads of one kind (the round mixes QSGD packets with sign packets or 'top' wire "
+           "packets)")
+    if type(agg.gar) is not FedAvg or gram_wanted(agg):
+        no("fed_avg for QSGD packets (sign_majority, Krum, the linear rules, the trim rules and "
+           "pc_analysis 'gram' have no consumer of QSGD packets)")
+    _one_device(agg, no)
+    _f32_weights(agg.gar, no)
+    hosts, n = _validated(payloads, codec._qsgd_check, n, no)
+    agg.curr_G = None
+    agg.agg_path = "wire-qsgd"
+    agg.agg_grad = qsgd_wire_round(agg, hosts, n, _device_of(agg)).cpu().numpy()
+
+
 def round_route(agg, clients):
     """Which of ``aggregate_grads``' packet routes the round takes, decided on the host (no GPU is
-    touched): ``(agg_path, k)`` with ``agg_path`` one of "gram", "sign-gram", "sign-trim", "sign"
-    and "ef-batch" (``k``: the common 'top' count of "gram" and "ef-batch", else None), or None
+    touched): ``(agg_path, k)`` with ``agg_path`` one of "gram", "sign-gram", "sign-trim", "sign",
+    "qsgd" and "ef-batch" (``k``: the common 'top' count of "gram" and "ef-batch", else None), or None
     for the stream / dense tail.  A round that a scheme or an opt-in key claims but whose
     conditions fail raises that route's refusal (no dense fallback).  The predicates are read in
     this order, so a round of 'sign' clients under a scheme without a consumer of sign packets is
@@ -1043,6 +1168,8 @@ def round_route(agg, clients):
         return "gram", gram_route_k(agg, clients)
     if sign:
         return "sign", None
+    if qsgd_route(agg, clients):
+        return "qsgd", None
     k = ef_batch_k(agg, clients)
     return None if k is None else ("ef-batch", k)
 
@@ -1072,6 +1199,8 @@ def aggregate_grads(self, clients: List, input_feature: np.ndarray = None,
             out = gram_round(self, clients, n, k, dev)
         elif self.agg_path == "sign":
             out = sign_round(self, clients, n, dev)
+        elif self.agg_path == "qsgd":               # dense-fold's bits
+            out = qsgd_round(self, clients, n, dev)
         elif self.agg_path == "ef-batch":           # dense-fold's bits
             w = self.gar._weights(len(clients), np.float32)         # gar.py:37-42 (persisted)
             out = ef_batch_fold(self, clients, n, k, w, dev)
@@ -1231,6 +1360,10 @@ def aggregate_wire(self, payloads, n: Optional[int] = None) -> None:
     * sign payloads under ``fed_avg`` (folded in groups, ``codec.fold_sign``) or ``sign_majority``
       (voted over, all resident): "wire-sign".  Every other scheme refuses sign payloads, and a
       round that mixes the two payload kinds is refused.
+    * QSGD payloads (``codec.pack_qsgd``) under ``fed_avg``: validated by
+      ``fc_qsgd_wire_validate``, uploaded and folded in groups (``codec.decode_accumulate_qsgd``):
+      "wire-qsgd", the bits of ``aggregate_grads``' "qsgd" route on the same clients.  Every other
+      scheme refuses them, and so is a round that mixes them with another payload kind.
     Hierarchies, several devices, payloads of differing n and a round that does not fit raise
     ``NotImplementedError`` naming the condition."""
     no = _wire_no
@@ -1242,6 +1375,9 @@ def aggregate_wire(self, payloads, n: Optional[int] = None) -> None:
         no("pc_analysis off or 'gram' (the randomized SVD of G is outside the hot path)")
     _no_hierarchies(self, no)
     gar = self.gar
+    qsgd_kinds = [codec.is_qsgd_payload(raw) for raw in payloads]
+    if any(qsgd_kinds):
+        return _aggregate_wire_qsgd(self, payloads, qsgd_kinds, n)
     kinds = [codec.is_sign_payload(raw) for raw in payloads]
     sign = any(kinds)
     trim = sign and sign_trim_wanted(self)

@@ -1869,6 +1869,7 @@ class QsgdPacket:
     hdr: torch.Tensor            # uint8[HDR_BYTES]
     n: int
     bits: int
+    buf: Optional[torch.Tensor] = None     # qsgd_from_host: the uploaded payload both live in
 
     @classmethod
     def alloc(cls, n: int, bits: int, device) -> "QsgdPacket":
@@ -1894,11 +1895,27 @@ _QSGD_WS = {}
 
 
 def encode_qsgd(g: torch.Tensor, bits: int, *, seed: int = 0, offset: int = 0,
-                packet: Optional[QsgdPacket] = None) -> QsgdPacket:
-    """QSGD codes of a device gradient (two streaming passes: ||g||, then quantise)."""
+                packet: Optional[QsgdPacket] = None, residual: Optional[torch.Tensor] = None,
+                residual_out: Optional[torch.Tensor] = None):
+    """QSGD codes of a device gradient (two streaming passes: ||g||, then quantise).
+
+    With ``residual`` or ``residual_out`` given (error feedback, fc_qsgd_encode_ef) the packet is
+    that of ``a = fl32(g + residual)`` (``a = g`` without a residual) and the same two passes also
+    write the new residual ``e' = fl32(a - q)``, ``q`` what :func:`decode_qsgd` gives for the packet
+    (into ``residual_out``, which may not overlap ``g`` or ``residual``; allocated when None); the
+    call then returns ``(packet, new residual)`` as :func:`encode_sign` does.  Without either it
+    returns the packet alone."""
     lib = L.load()
     _require_cuda_f32(g)
     n, dev = g.numel(), g.device
+    want = residual is not None or residual_out is not None
+    for name, t in (("residual", residual), ("residual_out", residual_out)):
+        if t is not None:
+            _require_cuda_f32(t, name)
+            if t.numel() != n or t.device != dev:
+                raise ValueError(f"{name} must have g's length and device")
+    if want and residual_out is None:
+        residual_out = torch.empty(n, dtype=torch.float32, device=dev)
     if packet is None:
         packet = QsgdPacket.alloc(n, bits, dev)
     key = (dev.index if dev.index is not None else torch.cuda.current_device(),
@@ -1907,6 +1924,11 @@ def encode_qsgd(g: torch.Tensor, bits: int, *, seed: int = 0, offset: int = 0,
     if ws is None:
         ws = _QSGD_WS[key] = torch.zeros(int(lib.fc_qsgd_workspace_bytes()), dtype=torch.uint8,
                                          device=dev)
+    if want:
+        L.check(lib.fc_qsgd_encode_ef(_vp(g), _vp(residual), _vp(residual_out), n, bits, seed, offset,
+                                      _vp(packet.codes), packet.codes.numel(), _vp(packet.hdr),
+                                      _vp(ws), ws.numel(), _stream(dev)), "fc_qsgd_encode_ef")
+        return packet, residual_out
     L.check(lib.fc_qsgd_encode(_vp(g), n, bits, seed, offset, _vp(packet.codes),
                                packet.codes.numel(), _vp(packet.hdr), _vp(ws), ws.numel(),
                                _stream(dev)), "fc_qsgd_encode")
@@ -1944,6 +1966,89 @@ def decode_accumulate_qsgd(packets: Sequence[QsgdPacket], weights, out: Optional
                                           int(continue_sum), _stream(dev)),
             "fc_qsgd_decode_accumulate")
     return out
+
+
+def qsgd_wire_bytes(n: int, bits: int) -> int:
+    """The size of a QSGD packet's wire form: 128 + 4 (fc_qsgd_code_words(n, bits) rounded up to a
+    multiple of 4); ``ValueError`` for bits outside [1, 14]."""
+    total = int(L.load().fc_qsgd_wire_bytes(n, bits))
+    if total == 0:
+        raise ValueError(f"bits={bits} outside [1, 14]")
+    return total
+
+
+def pack_qsgd(packet: QsgdPacket) -> torch.Tensor:
+    """The wire form of a QSGD packet as a device uint8 tensor (include/fedcodec.h): the 32 fixed
+    bytes, the device header, the codes and the zero pad words: copies only, no kernel, no
+    synchronisation."""
+    if not isinstance(packet, QsgdPacket):
+        raise TypeError("a QSGD packet expected (codec.encode_qsgd, codec.qsgd_from_host)")
+    lib = L.load()
+    dev = packet.codes.device
+    words = int(lib.fc_qsgd_code_words(packet.n, packet.bits))
+    total = qsgd_wire_bytes(packet.n, packet.bits)
+    if packet.codes.numel() < words:
+        raise ValueError("the packet's codes are shorter than fc_qsgd_code_words(n, bits)")
+    fixed = np.zeros(32, dtype=np.uint8)
+    fixed[:8].view(np.uint32)[:] = (L.QSGD_MAGIC, 1)
+    fixed[8:16].view(np.uint64)[0] = total
+    buf = torch.empty(total, dtype=torch.uint8, device=dev)
+    end = L.WIRE_HDR_BYTES + 4 * words
+    buf[:32].copy_(torch.from_numpy(fixed))
+    buf[32:L.WIRE_HDR_BYTES].copy_(packet.hdr)
+    buf[L.WIRE_HDR_BYTES:end].copy_(packet.codes[:words].view(torch.uint8))
+    if end < total:
+        buf[end:].zero_()
+    return buf
+
+
+def is_qsgd_payload(data) -> bool:
+    """Do these host bytes start with the QSGD packet's magic?"""
+    arr = _host_bytes(data)
+    return arr.size >= 4 and int(arr[:4].view(np.uint32)[0]) == L.QSGD_MAGIC
+
+
+def _qsgd_check(data, n: Optional[int] = None):
+    """fc_qsgd_wire_validate on host bytes: (the bytes as a uint8 array, their
+    ``L.QsgdWireHdr``), or ``ValueError`` with the library's reason.  Touches no device."""
+    arr = _host_bytes(data)
+    if n is not None and int(n) < 1:
+        raise ValueError("n must be at least 1")
+    lib = L.load()
+    rc = lib.fc_qsgd_wire_validate(ctypes.c_void_p(arr.ctypes.data), arr.size, int(n) if n else 0)
+    if rc != L.FC_OK:
+        msg = lib.fc_last_error()
+        raise ValueError(msg.decode() if msg else "qsgd wire: invalid packet")
+    return arr, L.QsgdWireHdr.from_buffer_copy(arr[: L.WIRE_HDR_BYTES].tobytes())
+
+
+def _qsgd_upload(arr: np.ndarray, hdr, device=None, out: Optional[torch.Tensor] = None) -> QsgdPacket:
+    """The H2D copy of bytes :func:`_qsgd_check` has passed (into ``out``, a 16-byte aligned
+    uint8 device tensor of their size, when given); the packet's header and codes are views of it
+    (the codes at byte 128 of the buffer: 16-byte aligned, as the fold needs)."""
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    if arr.flags.writeable:
+        host = torch.from_numpy(arr)
+    else:                                          # e.g. bytes: only ever read, so no host copy
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", UserWarning)
+            host = torch.frombuffer(arr, dtype=torch.uint8)
+    if out is None:
+        buf = host.to(dev)
+    else:
+        _check_wire_buffer(out, dev, "out")
+        if out.numel() != arr.size:
+            raise ValueError("out must have the payload's size")
+        buf = out.copy_(host)
+    return QsgdPacket(codes=buf[L.WIRE_HDR_BYTES:].view(_U32), hdr=buf[32:L.WIRE_HDR_BYTES],
+                      n=int(hdr.pkt.n), bits=int(hdr.pkt.k), buf=buf)
+
+
+def qsgd_from_host(data, n: Optional[int] = None, device=None) -> QsgdPacket:
+    """Host bytes as a :class:`QsgdPacket` on ``device``: ALWAYS through ``fc_qsgd_wire_validate``
+    first (``ValueError`` with the library's reason; no device work has started then), then one
+    H2D copy.  ``n``: the length the packet must have."""
+    return _qsgd_upload(*_qsgd_check(data, n), device)
 
 
 # ---- NumPy's legacy MT19937 stream on the device (the reference's dropout draws) -------------

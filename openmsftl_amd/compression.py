@@ -8,6 +8,7 @@ Same constructor keys and defaults, same ``compress(grad, layer_wise=False)`` co
   * 'dropout-unbiased'  float64 result, fl64(g)/p                     (compression.py:55-60)
   * 'qsgd', unknown names, layer_wise=True -> NotImplementedError at call time (:24,62,76)
   * 'sign'              opt-in, not in the reference: the scaled sign, float32 (:meth:`Compression._sign`)
+  * 'qsgd' with ``"qsgd": "native"``  opt-in: the reference's commented formula (:meth:`Compression._qsgd`)
 The compute runs in hand-written HIP kernels (libfedcodec.so); there is no CPU fallback.
 
 RNG: by default ('rng': 'numpy') 'rand'/'dropout-*' draw from the process-global legacy
@@ -20,8 +21,8 @@ generates ``np.random.binomial``'s own MT19937 variates on the device (jump-ahea
 (Philox4x32-10 keyed by ``'seed'``, counter advanced per call) — no host RNG work, not
 stream-identical to the reference (documented in DESIGN.md).
 
-Error feedback (opt-in key ``'error_feedback': True``, 'top' and 'sign' on float32 gradients only; the
-reference keeps no state between calls): the object keeps on the device what its calls so far
+Error feedback (opt-in key ``'error_feedback': True``, 'top', 'sign' and native 'qsgd' on float32
+gradients only; the reference keeps no state between calls): the object keeps on the device what its calls so far
 dropped and adds it to the next gradient (:meth:`Compression._top_ef`, ``get_residual`` /
 ``set_residual`` / ``reset_residual``).
 
@@ -117,9 +118,11 @@ class Compression:
         if fn == 'sign':
             return self._sign(grad)
         if self.error_feedback:
+            if fn == 'qsgd' and self.qsgd == 'native':
+                return self._qsgd(grad)
             if fn != 'top':
-                raise NotImplementedError("error_feedback is built for 'top' and 'sign' only "
-                                          f"(got {fn!r})")
+                raise NotImplementedError("error_feedback is built for 'top' and 'sign' only, and "
+                                          f"for 'qsgd' with \"qsgd\": \"native\" (got {fn!r})")
             return self._top_ef(grad)
         if fn == 'qsgd' and self.qsgd == 'native':
             return self._qsgd(grad)
@@ -299,9 +302,10 @@ class Compression:
         """What a client sends instead of the dense ``compress(grad)``: the 'top' packet of a 1-D
         float32 gradient (NumPy array or CUDA tensor) in its wire form (include/fedcodec.h:
         encode, resolve, ``codec.pack``), as ``bytes``; for 'sign' the sign packet's wire form
-        (``codec.pack_sign``).  With ``"error_feedback": True`` the
-        packet is :meth:`_top_ef`'s (:meth:`_sign`'s) and the residual advances exactly as
-        ``compress`` advances it.  ``Aggregator.aggregate_wire`` takes a round of these.  Other
+        (``codec.pack_sign``), for native 'qsgd' the QSGD packet's (``codec.pack_qsgd``; the Philox
+        offset advances as ``compress`` advances it).  With ``"error_feedback": True`` the
+        packet is :meth:`_top_ef`'s (:meth:`_sign`'s, :meth:`_qsgd`'s) and the residual advances
+        exactly as ``compress`` advances it.  ``Aggregator.aggregate_wire`` takes a round of these.  Other
         codecs raise ``NotImplementedError`` (``codec.pack`` itself takes any idx/val packet)."""
         fn = self.compression_function
         if fn == 'sign':
@@ -309,9 +313,14 @@ class Compression:
             if pkt is None:
                 raise ValueError("compress_wire: empty gradient")
             return codec.pack_sign(pkt).cpu().numpy().tobytes()
+        if fn == 'qsgd' and self.qsgd == 'native':
+            pkt = self._qsgd_packet(grad)
+            if pkt is None:
+                raise ValueError("compress_wire: empty gradient")
+            return codec.pack_qsgd(pkt).cpu().numpy().tobytes()
         if fn != 'top':
-            raise NotImplementedError("compress_wire is built for 'top' only, and for 'sign' "
-                                      f"(got {fn!r})")
+            raise NotImplementedError("compress_wire is built for 'top' only, and for 'sign' and "
+                                      f"native 'qsgd' (got {fn!r})")
         L.load()
         if self.error_feedback:
             pkt = self._top_ef_packet(grad)
@@ -377,15 +386,47 @@ class Compression:
         self._residual = self._residual_spare = None
 
     def _qsgd(self, grad):
-        """compression.py:65-74 (opt-in): dense float32 result of the QSGD codec."""
+        """compression.py:65-74 (opt-in): dense float32 result of the QSGD codec.
+
+        With ``"error_feedback": True`` (the quantiser divides by tau, E[q] = g / tau: a
+        contraction, the form EF-signSGD defines error feedback for):
+
+            a = fl32(grad + residual);  q = QSGD of a;  residual = fl32(a - q)
+
+        in the encode's own two passes (codec.encode_qsgd, fc_qsgd_encode_ef).  The residual lives
+        on the device as :meth:`_top_ef`'s does (the same two buffers, ``get_residual`` /
+        ``set_residual`` / ``reset_residual``) and advances on EVERY call, as the Philox offset
+        does.  float32 gradients only; a non-finite gradient poisons the residual exactly as the
+        arithmetic above says."""
+        on_device = isinstance(grad, torch.Tensor)
+        pkt = self._qsgd_packet(grad)
+        if pkt is None:                            # an empty gradient
+            return grad.clone() if on_device else np.zeros_like(grad)
+        out = codec.decode_qsgd(pkt)
+        return out if on_device else out.cpu().numpy()
+
+    def _qsgd_packet(self, grad):
+        """The packet behind :meth:`_qsgd` (None for an empty gradient): the Philox offset and,
+        with error feedback, the residual advance here, once per call, whether the caller wants
+        the dense q or the wire form."""
         L.load()
         on_device = isinstance(grad, torch.Tensor)
         g = self._to_device(grad)
-        if g.numel() == 0:
-            return grad.clone() if on_device else np.zeros_like(grad)
-        pkt = codec.encode_qsgd(g, int(self.num_bits), seed=self.seed, offset=self._next_offset())
-        out = codec.decode_qsgd(pkt)
-        return out if on_device else out.cpu().numpy()
+        n = g.numel()
+        if n == 0:
+            return None
+        if not self.error_feedback:
+            return codec.encode_qsgd(g, int(self.num_bits), seed=self.seed, offset=self._next_offset())
+        if g.dtype != torch.float32:
+            raise NotImplementedError("error_feedback handles float32 gradients only "
+                                      f"(got {g.dtype})")
+        if g.data_ptr() % 16:
+            g = g.clone()
+        res, spare = self._ef_buffers(n, g.device)
+        pkt, new = codec.encode_qsgd(g, int(self.num_bits), seed=self.seed, offset=self._next_offset(),
+                                     residual=res, residual_out=spare)
+        self._ef_commit(res, new, not on_device)
+        return pkt
 
     def _rand_device(self, grad, n: int, k: int, on_device: bool):
         """'rand' with np.random.permutation(n)[:k] drawn on the device from np.random's state

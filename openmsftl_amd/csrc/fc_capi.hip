@@ -844,8 +844,7 @@ int fc_decode_accumulate_continue(const fc_packet_view* views_dev, int m, int fo
 }
 
 uint64_t fc_qsgd_code_words(uint64_t n, int bits) {
-  if (bits < 1 || bits > 14) return 0;
-  return (n + kQsgdElems - 1) / kQsgdElems * (uint64_t)(qsgd_width(bits) * kQsgdElems / 32);
+  return qsgd_code_words(n, bits);                             // fc_qsgd_host.h
 }
 size_t fc_qsgd_workspace_bytes(void) { return 64 + 8 * (size_t)kQsgdNormGrid; }
 
@@ -888,6 +887,69 @@ int fc_qsgd_encode(const float* g, uint64_t n, int bits, uint64_t seed, uint64_t
                      g, n, bits, seed, offset, hdr, codes);
   FC_LAUNCHED("k_qsgd_quant");
   return FC_OK;
+}
+
+static bool qsgd_overlap(const float* a, const float* b, uint64_t n) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b, len = (uintptr_t)(4 * n);
+  return x < y + len && y < x + len;
+}
+
+// fc_qsgd_encode on a = g + res_in, and e' = a - q into res_out: the same two launches, their
+// kernels instantiated over the source that adds (fc_qsgd.hip).  Every argument error is reported
+// before the first launch.
+int fc_qsgd_encode_ef(const float* g, const float* res_in, float* res_out, uint64_t n, int bits,
+                      uint64_t seed, uint64_t offset, uint32_t* codes, uint64_t code_words,
+                      fc_packet_hdr* hdr, void* ws, size_t ws_bytes, fc_stream_t stream) {
+  FC_CHECK(g && codes && hdr && ws, "NULL argument");
+  FC_CHECK(n >= 1 && n <= 0xffffffffull, "n=%llu outside [1, 2^32-1]", (unsigned long long)n);
+  FC_CHECK(bits >= 1 && bits <= 14, "bits=%d outside [1, 14]", bits);
+  FC_CHECK(((uintptr_t)g & 15) == 0 && ((uintptr_t)res_in & 15) == 0 && ((uintptr_t)res_out & 15) == 0 &&
+               ((uintptr_t)codes & 15) == 0,
+           "g, res_in, res_out and codes must be 16-byte aligned");
+  FC_CHECK(!res_out || !qsgd_overlap(res_out, g, n), "res_out may not overlap g");
+  FC_CHECK(!res_out || !res_in || !qsgd_overlap(res_out, res_in, n), "res_out may not overlap res_in");
+  FC_CHECK(code_words >= fc_qsgd_code_words(n, bits), "code_words %llu < %llu needed",
+           (unsigned long long)code_words, (unsigned long long)fc_qsgd_code_words(n, bits));
+  if (ws_bytes < fc_qsgd_workspace_bytes())
+    return fail(FC_ERR_WORKSPACE, "workspace %zu B < %zu B needed", ws_bytes, fc_qsgd_workspace_bytes());
+  if (!res_in && !res_out)
+    return fc_qsgd_encode(g, n, bits, seed, offset, codes, code_words, hdr, ws, ws_bytes, stream);
+  hipStream_t s = (hipStream_t)stream;
+  char* w = static_cast<char*>(ws);
+  uint64_t ng = (n / 4 + kBlock - 1) / kBlock;                 // fc_qsgd_encode's: the sum order
+  if (ng < 1) ng = 1;
+  if (ng > (uint64_t)kQsgdNormGrid) ng = kQsgdNormGrid;
+  double* partial = reinterpret_cast<double*>(w + 64);
+  uint32_t* ticket = reinterpret_cast<uint32_t*>(w);
+  {
+    TimedLaunch t(FC_TIME_SAMPLE, s);
+    if (res_in)
+      hipLaunchKernelGGL(k_qsgd_norm_ef, dim3((uint32_t)ng), dim3(kBlock), 0, s, g, res_in, n, bits, seed,
+                         offset, partial, ticket, hdr);
+    else
+      hipLaunchKernelGGL(k_qsgd_norm, dim3((uint32_t)ng), dim3(kBlock), 0, s, g, n, bits, seed, offset,
+                         partial, ticket, hdr);
+    FC_LAUNCHED("k_qsgd_norm_ef");
+  }
+  TimedLaunch t(FC_TIME_COMPACT, s);
+  const dim3 grid(stream_grid((n + kQsgdElems - 1) / kQsgdElems, FC_QSGD_QGRID));
+  if (res_in && res_out)
+    hipLaunchKernelGGL((k_qsgd_quant_ef<true, true>), grid, dim3(kBlock), 0, s, g, res_in, res_out, n, bits,
+                       seed, offset, hdr, codes);
+  else if (res_in)
+    hipLaunchKernelGGL((k_qsgd_quant_ef<true, false>), grid, dim3(kBlock), 0, s, g, res_in, res_out, n, bits,
+                       seed, offset, hdr, codes);
+  else
+    hipLaunchKernelGGL((k_qsgd_quant_ef<false, true>), grid, dim3(kBlock), 0, s, g, res_in, res_out, n, bits,
+                       seed, offset, hdr, codes);
+  FC_LAUNCHED("k_qsgd_quant_ef");
+  return FC_OK;
+}
+
+uint64_t fc_qsgd_wire_bytes(uint64_t n, int bits) { return qsgd_wire_bytes(n, bits); }
+
+int fc_qsgd_wire_validate(const void* host_bytes, size_t len, uint64_t n_expected) {
+  return fc::qsgd_wire_validate(host_bytes, len, n_expected, g_err, sizeof g_err);
 }
 
 int fc_qsgd_decode(const fc_packet_view* pkt, uint64_t n, float* out, fc_stream_t stream) {

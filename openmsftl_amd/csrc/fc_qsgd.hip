@@ -22,7 +22,13 @@
 //           packed little-endian, 32 / W codes per uint32;
 //   value = (float)(+-(norm / (s * tau)) * l_i)   (fp64 product, one rounding to fp32).
 // Bytes: encode 8N (norm pass + quantise pass) + N W / 8; decode N W / 8 + 4N.
+//
+// With error feedback (fc_qsgd_encode_ef) both passes read a = fl32(g + e) instead of g, added as
+// it is loaded, and the quantise pass also writes e' = fl32(a - value): 20N + N W / 8 bytes, against
+// 36N + 2 N W / 8 and three N-float temporaries for fc_ef_sum, encode, decode and a subtract.
+// The packet's word count, wire layout and host validator are in fc_qsgd_host.h.
 #include "fc_state.h"
+#include "fc_qsgd_host.h"
 
 namespace fc {
 
@@ -32,8 +38,6 @@ constexpr int kQsgdNormUnroll = 2;             // float4 loads in flight per thr
 // (Plain cache-allocating loads, so that a back-to-front quantise pass could re-read the norm
 // pass's tail from the Infinity Cache, measured slower: norm 98 -> 145 us at 128 M, and the
 // quantise no faster; profiles/r04_ab_qsgd.jsonl.)
-
-__host__ __device__ inline int qsgd_width(int bits) { return bits <= 2 ? 4 : bits <= 6 ? 8 : 16; }
 
 struct QsgdParams {                            // from the header (decode) or the encode args
   double norm, scale;                          // scale = norm / (s * tau)
@@ -47,11 +51,32 @@ __device__ __forceinline__ double qsgd_tau(double d, double s) {
   return 1.0 + (a < b ? a : b);
 }
 
+// ---- what is encoded: g itself, or a = fl32(g + e) added as it is loaded (the EfSrc idea of
+// fc_ef.hip).  Both passes are templates over the source, so a's norm is summed in the very
+// order g's is and its codes come from the very arithmetic: fc_qsgd_encode_ef's header and codes
+// are fc_qsgd_encode's on an array holding a.  The add is one IEEE add (__fadd_rn: never
+// contracted with the fp64 square or the fp32 product that follow it).
+struct QsgdSrc {
+  const float* __restrict__ g;
+  __device__ __forceinline__ float4 load4(uint64_t i) const { return load4_full(g + i); }
+  __device__ __forceinline__ float load1(uint64_t i) const { return g[i]; }
+};
+struct QsgdEfSrc {
+  const float* __restrict__ g;
+  const float* __restrict__ e;
+  __device__ __forceinline__ float4 load4(uint64_t i) const {
+    const float4 a = load4_full(g + i), b = load4_full(e + i);
+    return make_float4(__fadd_rn(a.x, b.x), __fadd_rn(a.y, b.y), __fadd_rn(a.z, b.z),
+                       __fadd_rn(a.w, b.w));
+  }
+  __device__ __forceinline__ float load1(uint64_t i) const { return __fadd_rn(g[i], e[i]); }
+};
+
 // ---- pass 1: ||g||_2 (fp64, fixed order), header -------------------------------------------
-__global__ __launch_bounds__(kBlock) void k_qsgd_norm(const float* __restrict__ g, uint64_t n,
-                                                      int bits, uint64_t seed, uint64_t offset,
-                                                      double* partial, uint32_t* ticket,
-                                                      fc_packet_hdr* hdr) {
+template <class Src>
+__device__ __forceinline__ void qsgd_norm_body(const Src src, uint64_t n, int bits, uint64_t seed,
+                                               uint64_t offset, double* partial, uint32_t* ticket,
+                                               fc_packet_hdr* hdr) {
   __shared__ double s_red[kBlock / 64];
   __shared__ uint32_t s_flag;
   const int tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
@@ -64,7 +89,7 @@ __global__ __launch_bounds__(kBlock) void k_qsgd_norm(const float* __restrict__ 
   for (; q + (kQsgdNormUnroll - 1) * stride < n4; q += kQsgdNormUnroll * stride) {
     float4 v[kQsgdNormUnroll];
 #pragma unroll
-    for (int u = 0; u < kQsgdNormUnroll; ++u) v[u] = load4_full(g + 4 * (q + u * stride));
+    for (int u = 0; u < kQsgdNormUnroll; ++u) v[u] = src.load4(4 * (q + u * stride));
 #pragma unroll
     for (int u = 0; u < kQsgdNormUnroll; ++u) {
       acc += (double)v[u].x * v[u].x; acc += (double)v[u].y * v[u].y;
@@ -72,12 +97,12 @@ __global__ __launch_bounds__(kBlock) void k_qsgd_norm(const float* __restrict__ 
     }
   }
   for (; q < n4; q += stride) {
-    const float4 v = load4_full(g + 4 * q);
+    const float4 v = src.load4(4 * q);
     acc += (double)v.x * v.x; acc += (double)v.y * v.y;
     acc += (double)v.z * v.z; acc += (double)v.w * v.w;
   }
   if (blockIdx.x == 0 && tid < (int)(n - 4 * n4)) {            // tail (< 4 elements)
-    const double t = g[4 * n4 + tid];
+    const double t = src.load1(4 * n4 + tid);
     acc += t * t;
   }
 #pragma unroll
@@ -111,6 +136,19 @@ __global__ __launch_bounds__(kBlock) void k_qsgd_norm(const float* __restrict__ 
     hdr->reserved[0] = hdr->reserved[1] = hdr->reserved[2] = 0;
     *ticket = 0;                                                  // for the next encode
   }
+}
+__global__ __launch_bounds__(kBlock) void k_qsgd_norm(const float* __restrict__ g, uint64_t n,
+                                                      int bits, uint64_t seed, uint64_t offset,
+                                                      double* partial, uint32_t* ticket,
+                                                      fc_packet_hdr* hdr) {
+  qsgd_norm_body(QsgdSrc{g}, n, bits, seed, offset, partial, ticket, hdr);
+}
+__global__ __launch_bounds__(kBlock) void k_qsgd_norm_ef(const float* __restrict__ g,
+                                                         const float* __restrict__ e, uint64_t n,
+                                                         int bits, uint64_t seed, uint64_t offset,
+                                                         double* partial, uint32_t* ticket,
+                                                         fc_packet_hdr* hdr) {
+  qsgd_norm_body(QsgdEfSrc{g, e}, n, bits, seed, offset, partial, ticket, hdr);
 }
 
 __device__ __forceinline__ QsgdParams qsgd_params(double norm, int bits, uint64_t n) {
@@ -164,21 +202,42 @@ __device__ __forceinline__ void qsgd_load8(const float* __restrict__ g, uint64_t
 // 116 us.  (Measured and kept out: one quad per thread, each quad computing its group's Philox
 // block: 140 us; 4 groups per thread and pass: 129 us; without Philox or without the code
 // arithmetic the pass is 2-3 us shorter: it waits on memory, profiles/r05_ab_qsgd.jsonl.)
-__device__ __forceinline__ float4 qsgd_load4(const float* __restrict__ g, uint64_t e, uint64_t n) {
-  if (e + 4 <= n) return load4_full(g + e);
+template <class Src>
+__device__ __forceinline__ float4 qsgd_load4(const Src& src, uint64_t e, uint64_t n) {
+  if (e + 4 <= n) return src.load4(e);
   float4 v;
-  v.x = e < n ? g[e] : 0.f; v.y = e + 1 < n ? g[e + 1] : 0.f;
-  v.z = e + 2 < n ? g[e + 2] : 0.f; v.w = e + 3 < n ? g[e + 3] : 0.f;
+  v.x = e < n ? src.load1(e) : 0.f; v.y = e + 1 < n ? src.load1(e + 1) : 0.f;
+  v.z = e + 2 < n ? src.load1(e + 2) : 0.f; v.w = e + 3 < n ? src.load1(e + 3) : 0.f;
   return v;
+}
+__device__ __forceinline__ void qsgd_store4(float* out, uint64_t e, uint64_t n, const float4& v) {
+  if (e + 4 <= n) {
+    __builtin_nontemporal_store(fc_f4v{v.x, v.y, v.z, v.w}, reinterpret_cast<fc_f4v*>(out + e));
+  } else {
+    if (e < n) out[e] = v.x;
+    if (e + 1 < n) out[e + 1] = v.y;
+    if (e + 2 < n) out[e + 2] = v.z;
+  }
 }
 __device__ __forceinline__ float qsgd_swap1(float v) {     // the value of lane ^ 1
   return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1,
                                                             0xf, 0xf, true));
 }
-template <bool F32, int W>
-__device__ __forceinline__ void qsgd_quant_pass(const float* __restrict__ g, uint64_t n,
+__device__ __forceinline__ float4 qsgd_swap4(const float4& v) {
+  return make_float4(qsgd_swap1(v.x), qsgd_swap1(v.y), qsgd_swap1(v.z), qsgd_swap1(v.w));
+}
+// Src: what is encoded (g, or g + e added as it is loaded).  OUT: also write the new residual
+// e'[t] = fl32(a[t] - q[t]), q[t] the value fc_qsgd_decode gives the element's code
+// (qsgd_value: the same fp64 product and rounding).  e' leaves in the layout of the loads: the
+// lane pairs swap it back, so each store instruction writes 16 B per lane, 1 KB contiguous per
+// wave (two halves 32 B apart per lane do not merge: see the decode below).  With OUT no lane
+// leaves before that second swap: a lane past the last group computes codes of zeros, which
+// nothing stores.
+template <bool F32, int W, class Src, bool OUT>
+__device__ __forceinline__ void qsgd_quant_pass(const Src src, uint64_t n,
                                                 uint64_t seed, uint64_t offset,
-                                                const QsgdParams& q, uint32_t* codes) {
+                                                const QsgdParams& q, uint32_t* codes,
+                                                float* res_out) {
   const uint64_t groups = (n + kQsgdElems - 1) / kQsgdElems;
   const uint64_t stride = (uint64_t)gridDim.x * kBlock;
   const uint32_t lane = threadIdx.x & 63u;
@@ -192,8 +251,8 @@ __device__ __forceinline__ void qsgd_quant_pass(const float* __restrict__ g, uin
     for (int u = 0; u < kQsgdQuantUnroll; ++u) {
       const uint64_t e0 = (w0 + u * stride) * kQsgdElems;
       if (e0 < n) {
-        lo[u] = qsgd_load4(g, e0 + 4 * lane, n);
-        hi[u] = qsgd_load4(g, e0 + 256 + 4 * lane, n);
+        lo[u] = qsgd_load4(src, e0 + 4 * lane, n);
+        hi[u] = qsgd_load4(src, e0 + 256 + 4 * lane, n);
       }
     }
 #pragma unroll
@@ -202,13 +261,12 @@ __device__ __forceinline__ void qsgd_quant_pass(const float* __restrict__ g, uin
       if (b >= groups) break;                                      // wave-uniform
       const bool odd = lane & 1u;
       const float4 give = odd ? lo[u] : hi[u];
-      float4 got;
-      got.x = qsgd_swap1(give.x); got.y = qsgd_swap1(give.y);
-      got.z = qsgd_swap1(give.z); got.w = qsgd_swap1(give.w);
+      const float4 got = qsgd_swap4(give);
       const float4 a = odd ? got : lo[u], c = odd ? hi[u] : got;
       const float xs[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
       const uint64_t t = b + (lane >> 1) + (odd ? 32u : 0u);
-      if (t >= groups) continue;
+      const bool live = t < groups;
+      if (!OUT && !live) continue;
       const uint64_t e = t * kQsgdElems;
       const uint4 r0 = philox_block(e >> 3, seed, offset);     // 8 x 16 dither bits
       const uint32_t wd[4] = {r0.x, r0.y, r0.z, r0.w};
@@ -218,37 +276,74 @@ __device__ __forceinline__ void qsgd_quant_pass(const float* __restrict__ g, uin
         const uint32_t h = (wd[j >> 1] >> (16 * (j & 1))) & 0xffffu;
         c8[j] = e + j >= n ? 0u : qsgd_code<F32>(xs[j], h, q);
       }
-      if (W == 4) {
-        uint32_t v = 0;
+      if (live) {
+        if (W == 4) {
+          uint32_t v = 0;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v |= c8[j] << (4 * j);
-        codes[t] = v;
-      } else if (W == 8) {
-        reinterpret_cast<uint2*>(codes)[t] = make_uint2(c8[0] | c8[1] << 8 | c8[2] << 16 | c8[3] << 24,
-                                                        c8[4] | c8[5] << 8 | c8[6] << 16 | c8[7] << 24);
-      } else {
-        reinterpret_cast<uint4*>(codes)[t] = make_uint4(c8[0] | c8[1] << 16, c8[2] | c8[3] << 16,
-                                                        c8[4] | c8[5] << 16, c8[6] | c8[7] << 16);
+          for (int j = 0; j < 8; ++j) v |= c8[j] << (4 * j);
+          codes[t] = v;
+        } else if (W == 8) {
+          reinterpret_cast<uint2*>(codes)[t] = make_uint2(c8[0] | c8[1] << 8 | c8[2] << 16 | c8[3] << 24,
+                                                          c8[4] | c8[5] << 8 | c8[6] << 16 | c8[7] << 24);
+        } else {
+          reinterpret_cast<uint4*>(codes)[t] = make_uint4(c8[0] | c8[1] << 16, c8[2] | c8[3] << 16,
+                                                          c8[4] | c8[5] << 16, c8[6] | c8[7] << 16);
+        }
+      }
+      if (OUT) {
+        const float4 ra = make_float4(__fsub_rn(a.x, qsgd_value(c8[0], q)), __fsub_rn(a.y, qsgd_value(c8[1], q)),
+                                      __fsub_rn(a.z, qsgd_value(c8[2], q)), __fsub_rn(a.w, qsgd_value(c8[3], q)));
+        const float4 rc = make_float4(__fsub_rn(c.x, qsgd_value(c8[4], q)), __fsub_rn(c.y, qsgd_value(c8[5], q)),
+                                      __fsub_rn(c.z, qsgd_value(c8[6], q)), __fsub_rn(c.w, qsgd_value(c8[7], q)));
+        const float4 rgive = odd ? ra : rc;
+        const float4 back = qsgd_swap4(rgive);                       // the first swap undone
+        const uint64_t e0 = b * kQsgdElems;
+        const float4 slo = odd ? back : ra, shi = odd ? rc : back;   // by value: no address taken
+        qsgd_store4(res_out, e0 + 4 * lane, n, slo);
+        qsgd_store4(res_out, e0 + 256 + 4 * lane, n, shi);
       }
     }
   }
 }
 
-__global__ __launch_bounds__(kBlock) void k_qsgd_quant(const float* __restrict__ g, uint64_t n,
-                                                       int bits, uint64_t seed, uint64_t offset,
-                                                       const fc_packet_hdr* hdr, uint32_t* codes) {
+template <class Src, bool OUT>
+__device__ __forceinline__ void qsgd_quant_body(const Src src, uint64_t n, int bits, uint64_t seed,
+                                                uint64_t offset, const fc_packet_hdr* hdr,
+                                                uint32_t* codes, float* res_out) {
   const QsgdParams q = qsgd_params(hdr->p, bits, n);
   const bool f32 = q.c32 != __builtin_inff();
   if (f32) {
-    if (q.width == 4) qsgd_quant_pass<true, 4>(g, n, seed, offset, q, codes);
-    else if (q.width == 8) qsgd_quant_pass<true, 8>(g, n, seed, offset, q, codes);
-    else qsgd_quant_pass<true, 16>(g, n, seed, offset, q, codes);
+    if (q.width == 4) qsgd_quant_pass<true, 4, Src, OUT>(src, n, seed, offset, q, codes, res_out);
+    else if (q.width == 8) qsgd_quant_pass<true, 8, Src, OUT>(src, n, seed, offset, q, codes, res_out);
+    else qsgd_quant_pass<true, 16, Src, OUT>(src, n, seed, offset, q, codes, res_out);
   } else {
-    if (q.width == 4) qsgd_quant_pass<false, 4>(g, n, seed, offset, q, codes);
-    else if (q.width == 8) qsgd_quant_pass<false, 8>(g, n, seed, offset, q, codes);
-    else qsgd_quant_pass<false, 16>(g, n, seed, offset, q, codes);
+    if (q.width == 4) qsgd_quant_pass<false, 4, Src, OUT>(src, n, seed, offset, q, codes, res_out);
+    else if (q.width == 8) qsgd_quant_pass<false, 8, Src, OUT>(src, n, seed, offset, q, codes, res_out);
+    else qsgd_quant_pass<false, 16, Src, OUT>(src, n, seed, offset, q, codes, res_out);
   }
 }
+__global__ __launch_bounds__(kBlock) void k_qsgd_quant(const float* __restrict__ g, uint64_t n,
+                                                       int bits, uint64_t seed, uint64_t offset,
+                                                       const fc_packet_hdr* hdr, uint32_t* codes) {
+  qsgd_quant_body<QsgdSrc, false>(QsgdSrc{g}, n, bits, seed, offset, hdr, codes, nullptr);
+}
+// fc_qsgd_encode_ef's pass: E the source adds res_in, OUT e' is written (not both false: that is
+// k_qsgd_quant)
+template <bool E, bool OUT>
+__global__ __launch_bounds__(kBlock) void k_qsgd_quant_ef(const float* __restrict__ g,
+                                                          const float* __restrict__ e, float* res_out,
+                                                          uint64_t n, int bits, uint64_t seed,
+                                                          uint64_t offset, const fc_packet_hdr* hdr,
+                                                          uint32_t* codes) {
+  if (E) qsgd_quant_body<QsgdEfSrc, OUT>(QsgdEfSrc{g, e}, n, bits, seed, offset, hdr, codes, res_out);
+  else qsgd_quant_body<QsgdSrc, OUT>(QsgdSrc{g}, n, bits, seed, offset, hdr, codes, res_out);
+}
+template __global__ void k_qsgd_quant_ef<true, true>(const float*, const float*, float*, uint64_t, int,
+                                                     uint64_t, uint64_t, const fc_packet_hdr*, uint32_t*);
+template __global__ void k_qsgd_quant_ef<true, false>(const float*, const float*, float*, uint64_t, int,
+                                                      uint64_t, uint64_t, const fc_packet_hdr*, uint32_t*);
+template __global__ void k_qsgd_quant_ef<false, true>(const float*, const float*, float*, uint64_t, int,
+                                                      uint64_t, uint64_t, const fc_packet_hdr*, uint32_t*);
 
 // ---- decode (ACC: FedAVG over packets in row order, from +0 as np.sum) ----------------------
 struct QsgdDecodeArgs {
