@@ -92,22 +92,17 @@ class WireHdr(ctypes.Structure):
 
 
 class SignWireHdr(ctypes.Structure):
-    """fc_sign_wire_hdr: the first 128 bytes of a sign packet's wire form."""
+    """fc_payload_hdr: the first 128 bytes of a sign or a QSGD packet's wire form."""
     _fields_ = [("magic", ctypes.c_uint32), ("version", ctypes.c_uint32),
                 ("total_bytes", ctypes.c_uint64), ("zero", ctypes.c_uint32 * 4), ("pkt", PacketHdr)]
 
 
-class QsgdWireHdr(ctypes.Structure):
-    """fc_qsgd_wire_hdr: the first 128 bytes of a QSGD packet's wire form."""
-    _fields_ = [("magic", ctypes.c_uint32), ("version", ctypes.c_uint32),
-                ("total_bytes", ctypes.c_uint64), ("zero", ctypes.c_uint32 * 4), ("pkt", PacketHdr)]
-
+QsgdWireHdr = SignWireHdr
 
 SIGN_MAGIC = 0x31534346            # "FCS1"
 QSGD_MAGIC = 0x31514346            # "FCQ1"
 WIRE_HDR_BYTES = 128
 assert ctypes.sizeof(SignWireHdr) == WIRE_HDR_BYTES
-assert ctypes.sizeof(QsgdWireHdr) == WIRE_HDR_BYTES
 assert ctypes.sizeof(WireJob) == 16
 assert ctypes.sizeof(WireHdr) == WIRE_HDR_BYTES
 assert ctypes.sizeof(PermState) == 2520

@@ -587,8 +587,8 @@ def _cached(agg, attr: str, key, count: int, make) -> list:
 
 def _slab_upload(agg, attr: str, upload, part, dev: torch.device) -> list:
     """Validated payloads (``(bytes, header)`` pairs) into the device slab cached at
-    ``agg.<attr>["slab"]``, 256-byte aligned each, by ``upload`` (``codec._wire_upload`` /
-    ``codec._sign_upload``): the packets are views of it."""
+    ``agg.<attr>["slab"]``, 256-byte aligned each, by ``upload`` (a ``codec.PayloadKind``'s): the
+    packets are views of it."""
     cache = agg.__dict__.setdefault(attr, {})
     offs = np.concatenate([[0], np.cumsum([codec.slab_bytes(a.size) for a, _ in part])])
     slab = cache.get("slab")
@@ -1011,29 +1011,6 @@ def sign_resident_round(agg, clients, n: int, dev: torch.device, trim: bool) -> 
                            lambda: _sign_encode_resident(agg, clients, n, dev))
 
 
-def sign_wire_round(agg, hosts, n: int, dev: torch.device) -> torch.Tensor:
-    """aggregate_wire's round of validated sign payloads (``hosts``: what ``codec._sign_check``
-    returned for each): uploaded into one cached device slab and folded in groups
-    (:func:`wire_fold_groups`, ``fed_avg``) or voted over, all resident (``sign_majority``)."""
-    gar, m = agg.gar, len(hosts)
-    if type(gar) is SignMajority:
-        _fit(agg, sum(codec.slab_bytes(a.size) for a, _ in hosts) + 4 * n, _wire_no, dev, "sign packets",
-             _MAJORITY_TAIL)
-        groups = [range(0, m)]
-        wts = None
-    else:
-        groups = wire_fold_groups([a.size for a, _ in hosts], n, _budget(agg, dev))
-        wts = gar._weights(m, np.float32)                               # gar.py:37-42 (persisted)
-    out = torch.empty(n, dtype=torch.float32, device=dev)
-    for gi, g in enumerate(groups):
-        pk = _slab_upload(agg, "_sign_wire", codec._sign_upload, hosts[g.start:g.stop], dev)
-        if wts is None:
-            gar.aggregate_packets(pk, out=out)
-        else:
-            codec.fold_sign(pk, [float(x) for x in wts[g.start:g.stop]], out=out, continue_sum=gi > 0)
-    return out
-
-
 # ---- rounds of QSGD clients: only their N W / 8-byte packets resident -------------------------
 def _qsgd_bits(C) -> Optional[int]:
     """num_bits of a client that compresses with the native 'qsgd' at an integer number of bits in
@@ -1113,42 +1090,6 @@ def qsgd_round(agg, clients, n: int, dev: torch.device) -> torch.Tensor:
                                      continue_sum=s > 0)
         agg.qsgd_groups += 1
     return out
-
-
-def qsgd_wire_round(agg, hosts, n: int, dev: torch.device) -> torch.Tensor:
-    """aggregate_wire's round of validated QSGD payloads (``hosts``: what ``codec._qsgd_check``
-    returned for each): uploaded group by group into one cached device slab
-    (:func:`wire_fold_groups`) and folded in row order, continuing the sum: the "qsgd" route's
-    bits."""
-    gar, m = agg.gar, len(hosts)
-    groups = wire_fold_groups([a.size for a, _ in hosts], n, _budget(agg, dev))
-    wts = gar._weights(m, np.float32)                                 # gar.py:37-42 (persisted)
-    out = torch.empty(n, dtype=torch.float32, device=dev)
-    agg.qsgd_groups = 0
-    for gi, g in enumerate(groups):
-        pk = _slab_upload(agg, "_qsgd_wire", codec._qsgd_upload, hosts[g.start:g.stop], dev)
-        codec.decode_accumulate_qsgd(pk, [float(x) for x in wts[g.start:g.stop]], out=out,
-                                     continue_sum=gi > 0)
-        agg.qsgd_groups += 1
-    return out
-
-
-def _aggregate_wire_qsgd(agg, payloads, kinds, n: Optional[int]) -> None:
-    """aggregate_wire for a round that holds QSGD payloads ("wire-qsgd"): every refusal that needs
-    no GPU, the host validation, then :func:`qsgd_wire_round`."""
-    no = _wire_no
-    if not all(kinds):
-        no("payloads of one kind (the round mixes QSGD packets with sign packets or 'top' wire "
-           "packets)")
-    if type(agg.gar) is not FedAvg or gram_wanted(agg):
-        no("fed_avg for QSGD packets (sign_majority, Krum, the linear rules, the trim rules and "
-           "pc_analysis 'gram' have no consumer of QSGD packets)")
-    _one_device(agg, no)
-    _f32_weights(agg.gar, no)
-    hosts, n = _validated(payloads, codec._qsgd_check, n, no)
-    agg.curr_G = None
-    agg.agg_path = "wire-qsgd"
-    agg.agg_grad = qsgd_wire_round(agg, hosts, n, _device_of(agg)).cpu().numpy()
 
 
 def round_route(agg, clients):
@@ -1320,8 +1261,25 @@ def wire_fold_groups(sizes, n: int, budget_bytes: int) -> List[range]:
     return groups
 
 
+#: per payload kind: the aggregator's slab cache and codec's FedAVG fold of the uploaded packets
+_WIRE_FOLD = {"top": ("_wire_packets", "fold_wire"), "sign": ("_sign_wire", "fold_sign"),
+              "qsgd": ("_qsgd_wire", "decode_accumulate_qsgd")}
+
+
+def _fold_groups(agg, hosts, groups, n: int, dev: torch.device, upload, fold) -> torch.Tensor:
+    """aggregate_wire's FedAVG of validated payloads: group by group in row order ``upload`` puts a
+    group on the device (its packets) and ``fold`` adds them to the sum, which continues from group
+    to group."""
+    wts = agg.gar._weights(len(hosts), np.float32)                  # gar.py:37-42 (persisted)
+    out = torch.empty(n, dtype=torch.float32, device=dev)
+    for gi, g in enumerate(groups):
+        fold(upload(hosts[g.start:g.stop]), [float(x) for x in wts[g.start:g.stop]], out=out,
+             continue_sum=gi > 0)
+    return out
+
+
 def _validated(payloads, check, n: Optional[int], no):
-    """Every payload through ``check`` (``codec._wire_check`` / ``codec._sign_check``) on the host:
+    """Every payload through ``check`` (a ``codec.PayloadKind``'s) on the host:
     (the ``(bytes, header)`` pairs, their common n).  A bad payload is a ``ValueError`` naming its
     position and the reason."""
     hosts = []
@@ -1375,15 +1333,23 @@ def aggregate_wire(self, payloads, n: Optional[int] = None) -> None:
         no("pc_analysis off or 'gram' (the randomized SVD of G is outside the hot path)")
     _no_hierarchies(self, no)
     gar = self.gar
-    qsgd_kinds = [codec.is_qsgd_payload(raw) for raw in payloads]
-    if any(qsgd_kinds):
-        return _aggregate_wire_qsgd(self, payloads, qsgd_kinds, n)
-    kinds = [codec.is_sign_payload(raw) for raw in payloads]
-    sign = any(kinds)
-    trim = sign and sign_trim_wanted(self)
-    if sign:
-        if not all(kinds):
-            no("payloads of one kind (the round mixes sign packets and 'top' wire packets)")
+    # ---- one kind of payload ----
+    TOP, SIGN, QSGD = codec.TOP, codec.SIGN, codec.QSGD
+    kinds = [codec.kind_of(raw) for raw in payloads]
+    kind = QSGD if QSGD in kinds else SIGN if SIGN in kinds else TOP
+    if any(k is not kind for k in kinds):
+        no("payloads of one kind (the round mixes "
+           + ("QSGD packets with sign packets or 'top' wire packets)" if kind is QSGD
+              else "sign packets and 'top' wire packets)"))
+    # ---- the kind's consumers under this scheme; family: all of the round resident ----
+    trim = kind is SIGN and sign_trim_wanted(self)
+    what, many = "packets", "payloads for the gram route"
+    if kind is QSGD:
+        family = False
+        if type(gar) is not FedAvg or gram_wanted(self):
+            no("fed_avg for QSGD packets (sign_majority, Krum, the linear rules, the trim rules and "
+               "pc_analysis 'gram' have no consumer of QSGD packets)")
+    elif kind is SIGN:
         family = sign_geometry_wanted(self) or trim
         if (type(gar) not in (FedAvg, SignMajority) or gram_wanted(self)) and not family:
             no("fed_avg or sign_majority for sign packets (Krum, the linear rules, the trim rules "
@@ -1394,7 +1360,6 @@ def aggregate_wire(self, payloads, n: Optional[int] = None) -> None:
         if not family and type(gar) is not FedAvg:
             no("the device FedAvg, Krum, spectral_gram, geometric_median, centered_clip, trimmed_mean "
                "or coordinate_median")
-        what, many = "packets", "payloads for the gram route"
     family_no = _sign_trim_no if trim else no      # the sign-trim route names its own refusals
     _one_device(self, no)
     if type(gar) is SignMajority or isinstance(gar, CoordinateTrim):
@@ -1403,58 +1368,53 @@ def aggregate_wire(self, payloads, n: Optional[int] = None) -> None:
     if family:
         _at_most(m, many, family_no)
     # ---- the host's part: every payload validated, one common n, a configured budget ----
-    hosts, n = _validated(payloads, codec._sign_check if sign else codec._wire_check, n, no)
-    if sign:
+    hosts, n = _validated(payloads, kind.check, n, no)
+    if kind is not TOP:
         self.curr_G = None
     if family:
         total = sum(codec.slab_bytes(a.size) for a, _ in hosts)
-        need = (_sign_resident_bytes(self, trim, n, m, total) if sign
+        need = (_sign_resident_bytes(self, trim, n, m, total) if kind is SIGN
                 else wire_resident_bytes(n, m, total, gar))
         _fit(self, need, family_no, what=what)
-    # ---- the device's part ----
-    if sign:
+    # ---- the device's part: a round of 'top' payloads is named once the device is known ----
+    if kind is SIGN:
         self.agg_path = "wire-sign" + ("" if not family else "-trim" if trim else "-gram")
+    elif kind is QSGD:
+        self.agg_path = "wire-qsgd"
     dev = _device_of(self)
-    if not sign:
+    if kind is TOP:
         self.agg_path = "wire"
         self.curr_G = None
+    slab, fold = _WIRE_FOLD[kind.name]
 
     def upload(part):
         """The payloads of one group into one cached device slab (256-byte aligned each)."""
-        return _slab_upload(self, "_wire_packets", codec._wire_upload, part, dev)
+        return _slab_upload(self, slab, kind.upload, part, dev)
 
-    def packets_for(count: int):
-        return _cached(self, "_wire_packets", (n, dev), count,
-                       lambda count: codec.Packet.alloc_batch(n, count, L.FC_FMT_IDXVAL, dev))
+    def unpacked(wires):
+        return codec.unpack(wires, _cached(
+            self, "_wire_packets", (n, dev), len(wires),
+            lambda count: codec.Packet.alloc_batch(n, count, L.FC_FMT_IDXVAL, dev)))
 
-    if sign and family:
-        out = _resident_round(self, need, family_no, dev, what=what, packets=lambda: _slab_upload(
-            self, "_sign_wire", codec._sign_upload, hosts, dev))
-    elif sign:
-        out = sign_wire_round(self, hosts, n, dev)
-    elif family:
-        out = _resident_round(self, need, no, dev,
-                              lambda: codec.unpack(upload(hosts), packets_for(m)))
-    elif _config(self).get("wire_fold", False):
-        wts = gar._weights(m, np.float32)                           # gar.py:37-42 (persisted)
-        groups = wire_fold_groups([a.size for a, _ in hosts], n, _budget(self, dev))
-        self.agg_path = "wire-fold"
+    if family:                                                      # all resident: Gram / trim family
+        out = _resident_round(self, need, family_no, dev, what=what, packets=lambda: (
+            upload(hosts) if kind is SIGN else unpacked(upload(hosts))))
+    elif type(gar) is SignMajority:                                 # all resident: the vote
+        _fit(self, sum(codec.slab_bytes(a.size) for a, _ in hosts) + 4 * n, no, dev, "sign packets",
+             _MAJORITY_TAIL)
         out = torch.empty(n, dtype=torch.float32, device=dev)
-        for gi, g in enumerate(groups):
-            wires = upload(hosts[g.start:g.stop])
-            codec.fold_wire(wires, wts[g.start:g.stop], out=out, continue_sum=gi > 0)
-            del wires
-    else:
-        wts = gar._weights(m, np.float32)                           # gar.py:37-42 (persisted)
+        gar.aggregate_packets(upload(hosts), out=out)
+    elif kind is TOP and not _config(self).get("wire_fold", False):  # unpacked, then folded
         group = wire_group(self, n, m, dev)
-        out = torch.empty(n, dtype=torch.float32, device=dev)
-        for gi, s in enumerate(range(0, m, group)):
-            part = hosts[s:s + group]
-            wires = upload(part)
-            pk = codec.unpack(wires, packets_for(len(part)))
-            codec.decode_accumulate(pk, [float(x) for x in wts[s:s + len(part)]], out=out,
-                                    continue_sum=gi > 0)
-            del wires
+        out = _fold_groups(self, hosts, [range(s, min(s + group, m)) for s in range(0, m, group)], n, dev,
+                           lambda part: unpacked(upload(part)), codec.decode_accumulate)
+    else:                                                           # folded as they are
+        groups = wire_fold_groups([a.size for a, _ in hosts], n, _budget(self, dev))
+        if kind is TOP:
+            self.agg_path = "wire-fold"
+        out = _fold_groups(self, hosts, groups, n, dev, upload, getattr(codec, fold))
+        if kind is QSGD:
+            self.qsgd_groups = len(groups)
     self.agg_grad = out.cpu().numpy()
 
 

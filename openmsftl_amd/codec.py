@@ -30,7 +30,7 @@ import threading
 import warnings
 import weakref
 from dataclasses import dataclass
-from typing import Optional, Sequence
+from typing import Callable, Optional, Sequence
 
 import numpy as np
 import torch
@@ -1143,7 +1143,7 @@ def wire_from_host(data, n: Optional[int] = None, device=None) -> WirePacket:
     on ``device``: ALWAYS through ``fc_wire_validate`` first (``ValueError`` with the library's
     reason; no device work has started then), then the H2D copy.  ``n``: the length the packet
     must have.  The only way host bytes become a WirePacket."""
-    return _wire_upload(*_wire_check(data, n), device)
+    return TOP.upload(*TOP.check(data, n), device)
 
 
 def _host_bytes(data) -> np.ndarray:
@@ -1160,38 +1160,85 @@ def _host_bytes(data) -> np.ndarray:
     raise TypeError("data must be bytes, a 1-D NumPy uint8 array or a 1-D CPU uint8 tensor")
 
 
-def _wire_check(data, n: Optional[int] = None):
-    """fc_wire_validate on host bytes: (the bytes as a uint8 array, their ``L.WireHdr``), or
-    ``ValueError`` with the library's reason.  Touches no device."""
+@dataclass(frozen=True)
+class PayloadKind:
+    """One kind of wire payload (:data:`TOP`, :data:`SIGN`, :data:`QSGD`): what tells it from the
+    others on the way from host bytes to a packet on the device."""
+    name: str                          # 'top' | 'sign' | 'qsgd'
+    magic: Optional[int]               # None: whatever the other kinds do not claim
+    validate: str                      # the library's host validator
+    hdr: type                          # the ctypes class of the first 128 bytes
+    tag: str                           # the library's prefix of every reason
+    packet: Callable                   # (device buffer, header, payload bytes) -> the packet object
+
+    def check(self, data, n: Optional[int] = None):
+        """The library's validator on host bytes: (the bytes as a uint8 array, their header), or
+        ``ValueError`` with the library's reason.  Touches no device."""
+        arr = _host_bytes(data)
+        if n is not None and int(n) < 1:
+            raise ValueError("n must be at least 1")
+        lib = L.load()
+        rc = getattr(lib, self.validate)(ctypes.c_void_p(arr.ctypes.data), arr.size, int(n) if n else 0)
+        if rc != L.FC_OK:
+            msg = lib.fc_last_error()
+            raise ValueError(msg.decode() if msg else f"{self.tag}: invalid packet")
+        return arr, self.hdr.from_buffer_copy(arr[: L.WIRE_HDR_BYTES].tobytes())
+
+    def upload(self, arr: np.ndarray, hdr, device=None, out: Optional[torch.Tensor] = None):
+        """The H2D copy of bytes :meth:`check` has passed (into ``out``, a 16-byte aligned uint8
+        device tensor of their size, when given); the packet's tensors are views of the copy."""
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        if arr.flags.writeable:
+            host = torch.from_numpy(arr)
+        else:                                          # e.g. bytes: only ever read, so no host copy
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore", UserWarning)
+                host = torch.frombuffer(arr, dtype=torch.uint8)
+        if out is None:
+            buf = host.to(dev)
+        else:
+            _check_wire_buffer(out, dev, "out")
+            if out.numel() != arr.size:
+                raise ValueError("out must have the payload's size")
+            buf = out.copy_(host)
+        return self.packet(buf, hdr, arr.size)
+
+
+TOP = PayloadKind("top", None, "fc_wire_validate", L.WireHdr, "wire",
+                  lambda buf, hdr, nbytes: WirePacket(n=int(hdr.pkt.n), buf=buf, nbytes=nbytes, k=int(hdr.pkt.k)))
+SIGN = PayloadKind("sign", L.SIGN_MAGIC, "fc_sign_wire_validate", L.SignWireHdr, "sign wire",
+                   lambda buf, hdr, nbytes: SignPacket(words=buf[L.WIRE_HDR_BYTES:].view(_U32),
+                                                       hdr=buf[32:L.WIRE_HDR_BYTES], n=int(hdr.pkt.n), buf=buf))
+# the codes at byte 128 of the buffer: 16-byte aligned, as the fold needs
+QSGD = PayloadKind("qsgd", L.QSGD_MAGIC, "fc_qsgd_wire_validate", L.QsgdWireHdr, "qsgd wire",
+                   lambda buf, hdr, nbytes: QsgdPacket(codes=buf[L.WIRE_HDR_BYTES:].view(_U32),
+                                                       hdr=buf[32:L.WIRE_HDR_BYTES], n=int(hdr.pkt.n),
+                                                       bits=int(hdr.pkt.k), buf=buf))
+
+
+def kind_of(data) -> PayloadKind:
+    """The kind these host bytes claim by their magic, read once: :data:`SIGN`, :data:`QSGD`, or
+    :data:`TOP` for anything else (its validator reports a bad magic itself)."""
     arr = _host_bytes(data)
-    if n is not None and int(n) < 1:
-        raise ValueError("n must be at least 1")
-    lib = L.load()
-    rc = lib.fc_wire_validate(ctypes.c_void_p(arr.ctypes.data), arr.size, int(n) if n else 0)
-    if rc != L.FC_OK:
-        msg = lib.fc_last_error()
-        raise ValueError(msg.decode() if msg else "wire: invalid packet")
-    return arr, L.WireHdr.from_buffer_copy(arr[: L.WIRE_HDR_BYTES].tobytes())
+    magic = int(arr[:4].view(np.uint32)[0]) if arr.size >= 4 else None
+    return SIGN if magic == SIGN.magic else QSGD if magic == QSGD.magic else TOP
 
 
-def _wire_upload(arr: np.ndarray, hdr, device=None, out: Optional[torch.Tensor] = None) -> WirePacket:
-    """The H2D copy of bytes :func:`_wire_check` has passed (into ``out``, a 16-byte aligned
-    uint8 device tensor of their size, when given)."""
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    if arr.flags.writeable:
-        host = torch.from_numpy(arr)
-    else:                                          # e.g. bytes: only ever read, so no host copy
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore", UserWarning)
-            host = torch.frombuffer(arr, dtype=torch.uint8)
-    if out is None:
-        buf = host.to(dev)
-    else:
-        _check_wire_buffer(out, dev, "out")
-        if out.numel() != arr.size:
-            raise ValueError("out must have the payload's size")
-        buf = out.copy_(host)
-    return WirePacket(n=int(hdr.pkt.n), buf=buf, nbytes=arr.size, k=int(hdr.pkt.k))
+def _pack_fixed(magic: int, hdr: torch.Tensor, words: torch.Tensor, total: int) -> torch.Tensor:
+    """The wire form of a sign or QSGD packet as a device uint8 tensor of ``total`` bytes: the 32
+    fixed bytes, the device header, the words and zero bytes after them: copies only, no kernel, no
+    synchronisation."""
+    fixed = np.zeros(32, dtype=np.uint8)
+    fixed[:8].view(np.uint32)[:] = (magic, 1)
+    fixed[8:16].view(np.uint64)[0] = total
+    buf = torch.empty(total, dtype=torch.uint8, device=words.device)
+    end = L.WIRE_HDR_BYTES + 4 * words.numel()
+    buf[:32].copy_(torch.from_numpy(fixed))
+    buf[32:L.WIRE_HDR_BYTES].copy_(hdr)
+    buf[L.WIRE_HDR_BYTES:end].copy_(words.view(torch.uint8))
+    if end < total:
+        buf[end:].zero_()
+    return buf
 
 
 def unpack(wires, packets=None):
@@ -1713,65 +1760,21 @@ def pack_sign(packet: SignPacket) -> torch.Tensor:
     """The wire form of a sign packet as a device uint8 tensor (include/fedcodec.h): the 32 fixed
     bytes, the device header and the words, three copies and no kernel, no synchronisation."""
     (packet,) = _check_sign_packets([packet])
-    dev = packet.words.device
     words = int(L.load().fc_sign_words(packet.n))
     total = L.WIRE_HDR_BYTES + 4 * words
-    fixed = np.zeros(32, dtype=np.uint8)
-    fixed[:8].view(np.uint32)[:] = (L.SIGN_MAGIC, 1)
-    fixed[8:16].view(np.uint64)[0] = total
-    buf = torch.empty(total, dtype=torch.uint8, device=dev)
-    buf[:32].copy_(torch.from_numpy(fixed))
-    buf[32:L.WIRE_HDR_BYTES].copy_(packet.hdr)
-    buf[L.WIRE_HDR_BYTES:].copy_(packet.words[:words].view(torch.uint8))
-    return buf
+    return _pack_fixed(SIGN.magic, packet.hdr, packet.words[:words], total)
 
 
 def is_sign_payload(data) -> bool:
     """Do these host bytes start with the sign packet's magic?"""
-    arr = _host_bytes(data)
-    return arr.size >= 4 and int(arr[:4].view(np.uint32)[0]) == L.SIGN_MAGIC
-
-
-def _sign_check(data, n: Optional[int] = None):
-    """fc_sign_wire_validate on host bytes: (the bytes as a uint8 array, their
-    ``L.SignWireHdr``), or ``ValueError`` with the library's reason.  Touches no device."""
-    arr = _host_bytes(data)
-    if n is not None and int(n) < 1:
-        raise ValueError("n must be at least 1")
-    lib = L.load()
-    rc = lib.fc_sign_wire_validate(ctypes.c_void_p(arr.ctypes.data), arr.size, int(n) if n else 0)
-    if rc != L.FC_OK:
-        msg = lib.fc_last_error()
-        raise ValueError(msg.decode() if msg else "sign wire: invalid packet")
-    return arr, L.SignWireHdr.from_buffer_copy(arr[: L.WIRE_HDR_BYTES].tobytes())
-
-
-def _sign_upload(arr: np.ndarray, hdr, device=None, out: Optional[torch.Tensor] = None) -> SignPacket:
-    """The H2D copy of bytes :func:`_sign_check` has passed (into ``out``, a 16-byte aligned
-    uint8 device tensor of their size, when given); the packet's header and words are views of it."""
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    if arr.flags.writeable:
-        host = torch.from_numpy(arr)
-    else:                                          # e.g. bytes: only ever read, so no host copy
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore", UserWarning)
-            host = torch.frombuffer(arr, dtype=torch.uint8)
-    if out is None:
-        buf = host.to(dev)
-    else:
-        _check_wire_buffer(out, dev, "out")
-        if out.numel() != arr.size:
-            raise ValueError("out must have the payload's size")
-        buf = out.copy_(host)
-    return SignPacket(words=buf[L.WIRE_HDR_BYTES:].view(_U32), hdr=buf[32:L.WIRE_HDR_BYTES],
-                      n=int(hdr.pkt.n), buf=buf)
+    return kind_of(data) is SIGN
 
 
 def sign_from_host(data, n: Optional[int] = None, device=None) -> SignPacket:
     """Host bytes as a :class:`SignPacket` on ``device``: ALWAYS through ``fc_sign_wire_validate``
     first (``ValueError`` with the library's reason; no device work has started then), then the
     H2D copy.  ``n``: the length the packet must have."""
-    return _sign_upload(*_sign_check(data, n), device)
+    return SIGN.upload(*SIGN.check(data, n), device)
 
 
 # ---- float64 gradients (attack_models.py:105-106 -> aggregation.py:61) ----------------------
@@ -1983,72 +1986,23 @@ def pack_qsgd(packet: QsgdPacket) -> torch.Tensor:
     synchronisation."""
     if not isinstance(packet, QsgdPacket):
         raise TypeError("a QSGD packet expected (codec.encode_qsgd, codec.qsgd_from_host)")
-    lib = L.load()
-    dev = packet.codes.device
-    words = int(lib.fc_qsgd_code_words(packet.n, packet.bits))
+    words = int(L.load().fc_qsgd_code_words(packet.n, packet.bits))
     total = qsgd_wire_bytes(packet.n, packet.bits)
     if packet.codes.numel() < words:
         raise ValueError("the packet's codes are shorter than fc_qsgd_code_words(n, bits)")
-    fixed = np.zeros(32, dtype=np.uint8)
-    fixed[:8].view(np.uint32)[:] = (L.QSGD_MAGIC, 1)
-    fixed[8:16].view(np.uint64)[0] = total
-    buf = torch.empty(total, dtype=torch.uint8, device=dev)
-    end = L.WIRE_HDR_BYTES + 4 * words
-    buf[:32].copy_(torch.from_numpy(fixed))
-    buf[32:L.WIRE_HDR_BYTES].copy_(packet.hdr)
-    buf[L.WIRE_HDR_BYTES:end].copy_(packet.codes[:words].view(torch.uint8))
-    if end < total:
-        buf[end:].zero_()
-    return buf
+    return _pack_fixed(QSGD.magic, packet.hdr, packet.codes[:words], total)
 
 
 def is_qsgd_payload(data) -> bool:
     """Do these host bytes start with the QSGD packet's magic?"""
-    arr = _host_bytes(data)
-    return arr.size >= 4 and int(arr[:4].view(np.uint32)[0]) == L.QSGD_MAGIC
-
-
-def _qsgd_check(data, n: Optional[int] = None):
-    """fc_qsgd_wire_validate on host bytes: (the bytes as a uint8 array, their
-    ``L.QsgdWireHdr``), or ``ValueError`` with the library's reason.  Touches no device."""
-    arr = _host_bytes(data)
-    if n is not None and int(n) < 1:
-        raise ValueError("n must be at least 1")
-    lib = L.load()
-    rc = lib.fc_qsgd_wire_validate(ctypes.c_void_p(arr.ctypes.data), arr.size, int(n) if n else 0)
-    if rc != L.FC_OK:
-        msg = lib.fc_last_error()
-        raise ValueError(msg.decode() if msg else "qsgd wire: invalid packet")
-    return arr, L.QsgdWireHdr.from_buffer_copy(arr[: L.WIRE_HDR_BYTES].tobytes())
-
-
-def _qsgd_upload(arr: np.ndarray, hdr, device=None, out: Optional[torch.Tensor] = None) -> QsgdPacket:
-    """The H2D copy of bytes :func:`_qsgd_check` has passed (into ``out``, a 16-byte aligned
-    uint8 device tensor of their size, when given); the packet's header and codes are views of it
-    (the codes at byte 128 of the buffer: 16-byte aligned, as the fold needs)."""
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    if arr.flags.writeable:
-        host = torch.from_numpy(arr)
-    else:                                          # e.g. bytes: only ever read, so no host copy
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore", UserWarning)
-            host = torch.frombuffer(arr, dtype=torch.uint8)
-    if out is None:
-        buf = host.to(dev)
-    else:
-        _check_wire_buffer(out, dev, "out")
-        if out.numel() != arr.size:
-            raise ValueError("out must have the payload's size")
-        buf = out.copy_(host)
-    return QsgdPacket(codes=buf[L.WIRE_HDR_BYTES:].view(_U32), hdr=buf[32:L.WIRE_HDR_BYTES],
-                      n=int(hdr.pkt.n), bits=int(hdr.pkt.k), buf=buf)
+    return kind_of(data) is QSGD
 
 
 def qsgd_from_host(data, n: Optional[int] = None, device=None) -> QsgdPacket:
     """Host bytes as a :class:`QsgdPacket` on ``device``: ALWAYS through ``fc_qsgd_wire_validate``
     first (``ValueError`` with the library's reason; no device work has started then), then one
     H2D copy.  ``n``: the length the packet must have."""
-    return _qsgd_upload(*_qsgd_check(data, n), device)
+    return QSGD.upload(*QSGD.check(data, n), device)
 
 
 # ---- NumPy's legacy MT19937 stream on the device (the reference's dropout draws) -------------

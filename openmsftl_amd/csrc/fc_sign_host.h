@@ -1,6 +1,7 @@
 // fc_sign_host.h — the scaled-sign packet (FC_CODEC_SIGN, FC_FMT_SIGN): its word count, its wire
 // layout and the host validator.  Plain C++17 with no HIP includes, so a host compiler takes it
-// alone (tests/sign_validate_main.cc); fc_sign.hip includes it for the same layout on the device.
+// alone (tests/payload_validate_main.cc); fc_sign.hip includes it for the same layout on the device.
+// What the validator shares with the other payload kinds is in fc_payload_host.h.
 //
 // The packet of a gradient of n elements is one float32 scale s and n sign bits, bit t % 32 of
 // uint32 word[t / 32] (little-endian, the convention of mask_bits), in sign_words(n) words:
@@ -8,40 +9,21 @@
 // past n and the pad words are zero.
 //
 // Wire form, one contiguous little-endian byte string whose layout is a function of n alone:
-//   0     fc_sign_wire_hdr (128 bytes): magic "FCS1", version 1, uint64 total_bytes, 16 zero bytes,
+//   0     fc_payload_hdr (128 bytes): magic "FCS1", version 1, uint64 total_bytes, 16 zero bytes,
 //         then the canonical fc_packet_hdr: codec FC_CODEC_SIGN, format FC_FMT_SIGN, n, k =
 //         n_entries = n, status OK, p = (double)s, every other field zero
 //   128   uint32 word[sign_words(n)]
 // The device readers follow no offset out of the payload: the only value they take from it is p.
 #pragma once
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-
-#include "../../include/fedcodec.h"
-
-#if defined(__HIPCC__)
-#define FC_SIGN_HD __host__ __device__
-#else
-#define FC_SIGN_HD
-#endif
+#include "fc_payload_host.h"
 
 namespace fc {
 
 constexpr uint32_t kSignMagic = 0x31534346u;      // "FCS1" read as a little-endian uint32
-constexpr uint32_t kSignVersion = 1;
-constexpr uint64_t kSignHdrBytes = 128;
+constexpr PayloadKind kSignKind = {"sign wire", kSignMagic, true};
 
-struct fc_sign_wire_hdr {
-  uint32_t magic, version;
-  uint64_t total_bytes;
-  uint32_t zero[4];
-  fc_packet_hdr pkt;
-};
-static_assert(sizeof(fc_sign_wire_hdr) == 128, "fc_sign_wire_hdr layout");
-
-FC_SIGN_HD inline uint64_t sign_words(uint64_t n) { return ((n + 31) / 32 + 3) & ~3ull; }
-FC_SIGN_HD inline uint64_t sign_wire_bytes(uint64_t n) { return kSignHdrBytes + 4 * sign_words(n); }
+FC_HD inline uint64_t sign_words(uint64_t n) { return ((n + 31) / 32 + 3) & ~3ull; }
+FC_HD inline uint64_t sign_wire_bytes(uint64_t n) { return kPayloadHdrBytes + 4 * sign_words(n); }
 
 // Is the double with these bits the exact image of a float32 (NaNs: of a float32 NaN)?  Bit
 // tests only: a conversion of an out-of-range double would be undefined.
@@ -56,67 +38,42 @@ inline bool sign_is_float32(uint64_t bits) {
   return (man & ((1ull << drop) - 1ull)) == 0;
 }
 
-template <typename T>
-inline T sign_rd(const unsigned char* p, uint64_t off) {     // the bytes may sit at any address
-  T v;
-  memcpy(&v, p + off, sizeof v);
-  return v;
-}
-
 // FC_OK, or FC_ERR_ARG with the reason in err.  No read goes past len.
 inline int sign_wire_validate(const void* bytes, size_t len, uint64_t n_expected, char* err,
                               size_t err_len) {
-#define FC_SIGN_BAD(...)                       \
-  do {                                         \
-    snprintf(err, err_len, __VA_ARGS__);       \
-    return FC_ERR_ARG;                         \
-  } while (0)
   typedef unsigned long long ull;
-  if (bytes == nullptr) FC_SIGN_BAD("sign wire: bytes is NULL");
+  // 1. the fixed header, and n (payload_open)
+  fc_payload_hdr h;
+  if (payload_open(kSignKind, bytes, len, n_expected, &h, err, err_len) != FC_OK) return FC_ERR_ARG;
   const unsigned char* p = static_cast<const unsigned char*>(bytes);
-  // 1. the fixed header
-  if (len < kSignHdrBytes)
-    FC_SIGN_BAD("sign wire: %llu bytes are shorter than the 128-byte header", (ull)len);
-  const fc_sign_wire_hdr h = sign_rd<fc_sign_wire_hdr>(p, 0);
-  if (h.magic != kSignMagic) FC_SIGN_BAD("sign wire: bad magic 0x%08x", h.magic);
-  if (h.version != kSignVersion) FC_SIGN_BAD("sign wire: unsupported version %u", h.version);
-  if (h.total_bytes != (uint64_t)len)
-    FC_SIGN_BAD("sign wire: total_bytes %llu but %llu bytes given", (ull)h.total_bytes, (ull)len);
-  if (h.zero[0] | h.zero[1] | h.zero[2] | h.zero[3])
-    FC_SIGN_BAD("sign wire: the reserved bytes 16..31 are not zero");
   // 2. the packet header
   const fc_packet_hdr& k = h.pkt;
   const uint64_t n = k.n;
-  if (n < 1) FC_SIGN_BAD("sign wire: n = 0");
-  if (n_expected != 0 && n != n_expected)
-    FC_SIGN_BAD("sign wire: n = %llu but %llu expected", (ull)n, (ull)n_expected);
-  if (k.codec != FC_CODEC_SIGN) FC_SIGN_BAD("sign wire: codec %u is not sign", k.codec);
-  if (k.format != FC_FMT_SIGN) FC_SIGN_BAD("sign wire: format %u is not sign", k.format);
-  if (k.k != k.n) FC_SIGN_BAD("sign wire: k = %u is not n = %u", k.k, k.n);
-  if (k.n_entries != k.n) FC_SIGN_BAD("sign wire: n_entries = %u is not n = %u", k.n_entries, k.n);
-  if (k.status != FC_STATUS_OK) FC_SIGN_BAD("sign wire: status %u is not OK", k.status);
+  if (k.codec != FC_CODEC_SIGN) FC_BAD("sign wire: codec %u is not sign", k.codec);
+  if (k.format != FC_FMT_SIGN) FC_BAD("sign wire: format %u is not sign", k.format);
+  if (k.k != k.n) FC_BAD("sign wire: k = %u is not n = %u", k.k, k.n);
+  if (k.n_entries != k.n) FC_BAD("sign wire: n_entries = %u is not n = %u", k.n_entries, k.n);
+  if (k.status != FC_STATUS_OK) FC_BAD("sign wire: status %u is not OK", k.status);
   if (k.thresh || k.lower || k.index_bits || k.n_definite || k.n_cand || k.seed || k.offset ||
       k.chunk || k.key_mode || k.reserved[0] || k.reserved[1] || k.reserved[2])
-    FC_SIGN_BAD("sign wire: a header field that must be zero is not");
-  const uint64_t pb = sign_rd<uint64_t>(reinterpret_cast<const unsigned char*>(&k.p), 0);
-  const bool p_nan = ((pb >> 52) & 0x7ff) == 0x7ff && (pb & 0xfffffffffffffull) != 0;
-  if ((pb >> 63) != 0 && !p_nan) FC_SIGN_BAD("sign wire: the scale p is negative");
-  if (!sign_is_float32(pb)) FC_SIGN_BAD("sign wire: the scale p is not a float32 value");
+    FC_BAD("sign wire: a header field that must be zero is not");
+  const uint64_t pb = payload_p_bits(k);
+  if (payload_p_negative(pb)) FC_BAD("sign wire: the scale p is negative");
+  if (!sign_is_float32(pb)) FC_BAD("sign wire: the scale p is not a float32 value");
   // 3. the geometry: a function of n alone
   if (sign_wire_bytes(n) != (uint64_t)len)
-    FC_SIGN_BAD("sign wire: total_bytes %llu is not the size of n = %llu (%llu)", (ull)len, (ull)n,
-                (ull)sign_wire_bytes(n));
+    FC_BAD("sign wire: total_bytes %llu is not the size of n = %llu (%llu)", (ull)len, (ull)n,
+           (ull)sign_wire_bytes(n));
   // 4. the tail bits and the pad words
   const uint64_t full = n / 32, words = sign_words(n);
   if (n % 32) {
-    const uint32_t w = sign_rd<uint32_t>(p, kSignHdrBytes + 4 * full);
-    if (w >> (n % 32)) FC_SIGN_BAD("sign wire: a bit at or past n = %llu is set", (ull)n);
+    const uint32_t w = payload_rd<uint32_t>(p, kPayloadHdrBytes + 4 * full);
+    if (w >> (n % 32)) FC_BAD("sign wire: a bit at or past n = %llu is set", (ull)n);
   }
   for (uint64_t i = (n + 31) / 32; i < words; ++i)
-    if (sign_rd<uint32_t>(p, kSignHdrBytes + 4 * i) != 0)
-      FC_SIGN_BAD("sign wire: pad word %llu is not zero", (ull)i);
+    if (payload_rd<uint32_t>(p, kPayloadHdrBytes + 4 * i) != 0)
+      FC_BAD("sign wire: pad word %llu is not zero", (ull)i);
   return FC_OK;
-#undef FC_SIGN_BAD
 }
 
 }  // namespace fc

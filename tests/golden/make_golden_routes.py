@@ -184,8 +184,9 @@ def wire_row(scheme, key, cond, raws):
     return [_outcome(agg.aggregate_wire, raws), repr(agg.agg_path)]
 
 
-def table():
-    """The whole table as the dict ``routes.json`` holds."""
+def tabulate(grads_fields, grads_rows, wire_fields, wire_rows):
+    """The dict a routes file holds.  ``grads_rows()`` / ``wire_rows()`` give every case's row of
+    outcomes; they run with the device sentinel in place."""
     from openmsftl_amd import aggregation as ag
     from openmsftl_amd import build
     build.build(verbose=False)
@@ -211,13 +212,19 @@ def table():
     saved = ag._device_of
     ag._device_of = _reach
     try:
-        g_rows, g_cases = fold(grads_row(*c[1:]) for c in grads_cases())
-        w_rows, w_cases = fold(wire_row(*c[1:]) for c in wire_cases())
+        g_rows, g_cases = fold(grads_rows())
+        w_rows, w_cases = fold(wire_rows())
     finally:
         ag._device_of = saved
-    return {"grads_fields": list(GRADS_FIELDS), "wire_fields": list(WIRE_FIELDS),
+    return {"grads_fields": list(grads_fields), "wire_fields": list(wire_fields),
             "outcomes": outcomes, "grads_rows": g_rows, "grads_cases": g_cases,
             "wire_rows": w_rows, "wire_cases": w_cases}
+
+
+def table():
+    """The whole table as the dict ``routes.json`` holds."""
+    return tabulate(GRADS_FIELDS, lambda: (grads_row(*c[1:]) for c in grads_cases()),
+                    WIRE_FIELDS, lambda: (wire_row(*c[1:]) for c in wire_cases()))
 
 
 def dumps(tab) -> str:

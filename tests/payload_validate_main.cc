@@ -1,26 +1,38 @@
-// Stand-alone driver of the wire format's host-side rules (openmsftl_amd/csrc/fc_wire_host.h), for
-// a host compiler with -fsanitize=address,undefined (tests/test_wire_host.py builds and runs it).
+// Stand-alone driver of the host-side rules of the three wire payload kinds
+// (openmsftl_amd/csrc/fc_wire_host.h, fc_sign_host.h, fc_qsgd_host.h over fc_payload_host.h), for a
+// host compiler with -fsanitize=address,undefined (tests/payload_standalone.py builds and runs it).
+// KIND is wire, sign or qsgd.
 //
-//   wire_validate_main LIST
-// LIST: one "n_expected path" per line.  Each payload is read into a heap block of exactly its
-// size, so a read past `len` lands in a redzone.  Prints one verdict line per payload:
-// "OK" or "BAD <reason>".
+//   payload_validate_main KIND LIST
+// LIST: one "n_expected path" per line.  Each payload is validated in a heap block of exactly its
+// size (one byte in front keeps it off malloc's alignment: the validator may not assume any), so a
+// read past `len` lands in a redzone.  Prints one verdict line per payload: "OK" or "BAD <reason>".
 //
-//   wire_validate_main --clamp LIST
-// LIST: one "n path" per line, n the length the reader expects.  The payload, again in a heap
-// block of exactly its size, goes through what the device readers (k_wire_unpack, the wire fold)
-// do with bytes nobody validated: wire_accept, then for every chunk wire_clamp and a read of every
-// idx and val entry of [st, st + cnt) through the section offsets.  Prints "REJECT", or
-// "ACCEPT E=<entries> exact=<1 if every chunk's clamp returned the stored words, else 0>"; exits
-// with 1 if a clamped range leaves [0, E) or its boundaries are out of order.
+//   payload_validate_main KIND --trunc LIST
+// The same, but every payload is validated at EVERY length 0 .. size, each prefix in a heap block
+// of exactly that length.  Prints per payload "TRUNC ok=<prefixes accepted> of=<prefixes tried>".
+//
+//   payload_validate_main wire --clamp LIST
+// LIST: one "n path" per line, n the length the reader expects.  The payload, in a heap block of
+// exactly its size and of the block's own alignment (as a device buffer has it), goes through what
+// the device readers (k_wire_unpack, the wire fold) do with bytes nobody validated: wire_accept,
+// then for every chunk wire_clamp and a read of every idx and val entry of [st, st + cnt) through
+// the section offsets.  Prints "REJECT", or "ACCEPT E=<entries> exact=<1 if every chunk's clamp
+// returned the stored words, else 0>"; exits with 1 if a clamped range leaves [0, E) or its
+// boundaries are out of order.
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <fstream>
 #include <sstream>
 #include <string>
 
+#include "../openmsftl_amd/csrc/fc_qsgd_host.h"
+#include "../openmsftl_amd/csrc/fc_sign_host.h"
 #include "../openmsftl_amd/csrc/fc_wire_host.h"
+
+typedef int (*validate_fn)(const void*, size_t, uint64_t, char*, size_t);
 
 static volatile unsigned long long g_sink;
 
@@ -69,10 +81,21 @@ static bool clamp_walk(const unsigned char* data, size_t size, unsigned long lon
   return true;
 }
 
+// `front` bytes before the payload in a heap block that ends where the payload ends
+static unsigned char* block_of(const unsigned char* src, size_t len, size_t front) {
+  unsigned char* block = static_cast<unsigned char*>(malloc(len + front));
+  if (len) memcpy(block + front, src, len);
+  return block;
+}
+
 int main(int argc, char** argv) {
-  const bool clamp = argc == 3 && std::string(argv[1]) == "--clamp";
-  if (argc != 2 && !clamp) {
-    fprintf(stderr, "usage: %s [--clamp] LIST\n", argv[0]);
+  const std::string kind = argc > 1 ? argv[1] : "", mode = argc == 4 ? argv[2] : "";
+  const validate_fn validate = kind == "wire" ? fc::wire_validate
+                               : kind == "sign" ? fc::sign_wire_validate
+                               : kind == "qsgd" ? fc::qsgd_wire_validate : nullptr;
+  const bool trunc = mode == "--trunc", clamp = mode == "--clamp" && kind == "wire";
+  if (!validate || (argc != 3 && !trunc && !clamp)) {
+    fprintf(stderr, "usage: %s wire|sign|qsgd [--trunc] LIST, or %s wire --clamp LIST\n", argv[0], argv[0]);
     return 2;
   }
   std::ifstream list(argv[argc - 1]);
@@ -96,25 +119,30 @@ int main(int argc, char** argv) {
     fseek(f, 0, SEEK_END);
     const long size = ftell(f);
     fseek(f, 0, SEEK_SET);
-    // the validator: one byte in front keeps the payload off malloc's alignment, it may not assume
-    // any.  The readers' path: the block's own alignment, as a device buffer has it.
-    const size_t front = clamp ? 0 : 1;
-    unsigned char* block = static_cast<unsigned char*>(malloc((size_t)size + front));
-    unsigned char* data = block + front;
+    unsigned char* data = static_cast<unsigned char*>(malloc((size_t)size + 1));
     if (size > 0 && fread(data, 1, (size_t)size, f) != (size_t)size) {
       fprintf(stderr, "short read of %s\n", path.c_str());
       return 2;
     }
     fclose(f);
     if (clamp) {
-      if (!clamp_walk(data, (size_t)size, n_expected)) return 1;
+      unsigned char* block = block_of(data, (size_t)size, 0);
+      const bool inside = clamp_walk(block, (size_t)size, n_expected);
+      free(block);
+      if (!inside) return 1;
     } else {
       char err[512] = "";
-      const int rc = fc::wire_validate(data, (size_t)size, n_expected, err, sizeof err);
-      if (rc == FC_OK) printf("OK\n");
+      unsigned long long ok = 0;
+      for (long len = trunc ? 0 : size; len <= size; ++len) {
+        unsigned char* block = block_of(data, (size_t)len, 1);
+        ok += validate(block + 1, (size_t)len, n_expected, err, sizeof err) == FC_OK;
+        free(block);
+      }
+      if (trunc) printf("TRUNC ok=%llu of=%ld\n", ok, size + 1);
+      else if (ok) printf("OK\n");
       else printf("BAD %s\n", err);
     }
-    free(block);
+    free(data);
   }
   return 0;
 }

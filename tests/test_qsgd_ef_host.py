@@ -7,13 +7,12 @@ Run:  python -m pytest tests/test_qsgd_ef_host.py -m "not gpu" -q
 No GPU is needed: the library loads without one (tests/test_lib_abi.py).  Payloads come from
 tests/qsgd_ef_model.py; one mutation per rule of the validator's list (include/fedcodec.h) must be
 rejected with the message of that rule.  The same corpus, and every truncation of the valid
-payloads, goes through the stand-alone program tests/qsgd_validate_main.cc, built with the host
+payloads, goes through the stand-alone program tests/payload_validate_main.cc, built with the host
 compiler and -fsanitize=address,undefined: the same verdicts and no sanitizer report.
 """
 import ctypes
 import os
 import re
-import shutil
 import subprocess
 import types
 
@@ -22,6 +21,7 @@ import pytest
 
 import qsgd_ef_model as qm
 from oracle import qsgd_oracle as qo
+from payload_standalone import run, standalone  # noqa: F401  (standalone: a fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "fedcodec.h")
@@ -331,77 +331,36 @@ def test_the_validators_reject_each_others_bytes(lib):
         assert fn(ctypes.cast(buf, ctypes.c_void_p), len(raw), 0) == -1
         assert b"bad magic" in lib.fc_last_error()
     with pytest.raises(ValueError, match="bad magic"):
-        codec._wire_check(raw)
+        codec.TOP.check(raw)
     with pytest.raises(ValueError, match="bad magic"):
-        codec._sign_check(raw)
+        codec.SIGN.check(raw)
     sign = sm.pack(129, 1.0, sm.words_of(np.ones(129, bool)))
     top = wm.pack(po.build_idxval(129, np.array([3]), F([1.0]), thresh=0, codec=po.CODEC_TOP, k=1))
     for other in (sign, top):
         rc, msg = validate(lib, other)
         assert rc == -1 and "bad magic" in msg
         with pytest.raises(ValueError, match="qsgd wire: bad magic"):
-            codec._qsgd_check(other)
+            codec.QSGD.check(other)
         assert not codec.is_qsgd_payload(other)
     assert codec.is_qsgd_payload(raw) and not codec.is_sign_payload(raw)
     assert not codec.is_qsgd_payload(b"FCQ") and not codec.is_qsgd_payload(b"FCS1" + raw[4:])
-    a, h = codec._qsgd_check(raw, n)
+    a, h = codec.QSGD.check(raw, n)
     assert int(h.pkt.n) == n and int(h.pkt.k) == 2 and a.size == len(raw)
     with pytest.raises(ValueError, match="expected"):
-        codec._qsgd_check(raw, n + 1)
+        codec.QSGD.check(raw, n + 1)
     with pytest.raises(ValueError, match="at least 1"):
-        codec._qsgd_check(raw, 0)
+        codec.QSGD.check(raw, 0)
     assert codec.qsgd_wire_bytes(n, 2) == len(raw)
     with pytest.raises(ValueError, match="bits=15"):
         codec.qsgd_wire_bytes(n, 15)
 
 
 # ---- the same corpus through the sanitized stand-alone program --------------------------------
-def _compiler():
-    for c in ("c++", "g++", "clang++"):
-        if shutil.which(c):
-            return c
-    raise RuntimeError("no host C++ compiler")
-
-
-@pytest.fixture(scope="module")
-def standalone(tmp_path_factory):
-    """(path of the program, sanitized?): built with -fsanitize=address,undefined, or without
-    when the sanitizer runtime does not link on this machine."""
-    d = tmp_path_factory.mktemp("qsgd_validate")
-    exe = str(d / "qsgd_validate_main")
-    src = os.path.join(ROOT, "tests", "qsgd_validate_main.cc")
-    base = [_compiler(), "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", src, "-o", exe]
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"]
-    for extra in (["-static-libasan", "-static-libubsan"], ["-static-libsan"], []):
-        r = subprocess.run(base + san + extra, capture_output=True, text=True)
-        if r.returncode == 0:
-            return exe, True
-    print("sanitizer build failed, building without:\n" + r.stderr[-2000:])
-    subprocess.run(base, check=True)
-    return exe, False
-
-
-def _run(exe, args, tmp_path, corpus):
-    lines = []
-    for i, (_, raw, n_expected) in enumerate(corpus):
-        path = tmp_path / f"payload_{i:03d}.bin"
-        path.write_bytes(raw)
-        lines.append(f"{n_expected} {path}")
-    (tmp_path / "list.txt").write_text("\n".join(lines) + "\n")
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, *args, str(tmp_path / "list.txt")], capture_output=True, text=True, env=env)
-    assert r.returncode == 0, r.stderr[-4000:]
-    assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
-    out = r.stdout.splitlines()
-    assert len(out) == len(corpus)
-    return out
-
-
 def test_the_corpus_through_the_sanitized_standalone_program(lib, standalone, tmp_path):
     exe, sanitized = standalone
     corpus = [(name, raw, n) for name, (raw, n) in sorted(accepted_payloads().items())]
     corpus += [(name,) + mutations()[name][:2] for name in MUTATIONS]
-    for (name, raw, n_expected), got in zip(corpus, _run(exe, [], tmp_path, corpus)):
+    for (name, raw, n_expected), got in zip(corpus, run(exe, ["qsgd"], tmp_path, corpus)):
         rc, msg = validate(lib, raw, n_expected)
         assert got == ("OK" if rc == 0 else "BAD " + msg), name         # the library's verdict
         if name in mutations():
@@ -417,7 +376,7 @@ def test_every_truncation_through_the_sanitized_standalone_program(standalone, t
     exe, sanitized = standalone
     corpus = [(name, raw, 0) for name, (raw, n) in sorted(accepted_payloads().items()) if n <= 100]
     corpus += [("mutated " + name, mutations()[name][0], 0) for name in MUTATIONS[:6]]
-    for (name, raw, _), got in zip(corpus, _run(exe, ["--trunc"], tmp_path, corpus)):
+    for (name, raw, _), got in zip(corpus, run(exe, ["qsgd", "--trunc"], tmp_path, corpus)):
         want = 0 if name.startswith("mutated ") else 1
         assert got == f"TRUNC ok={want} of={len(raw) + 1}", (name, got)
     print(f"{len(corpus)} payloads, sanitized build: {sanitized}")

@@ -4,23 +4,20 @@ Run:  python -m pytest tests/test_wire_host.py -m "not gpu" -q
 
 No GPU is needed: the library loads without one (tests/test_lib_abi.py).  Payloads come from
 tests/wire_model.py; one mutation per check of the validator's list (include/fedcodec.h) must be
-rejected with the message of that check.  The same corpus goes through the stand-alone program
-tests/wire_validate_main.cc, built with the host compiler and -fsanitize=address,undefined:
-the same verdicts and no sanitizer report.
+rejected with the message of that check.  The same corpus, and every truncation of small valid
+payloads, goes through the stand-alone program tests/payload_validate_main.cc, built with the host
+compiler and -fsanitize=address,undefined: the same verdicts and no sanitizer report.
 """
 import ctypes
-import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import wire_model as wm
 from oracle import packet_oracle as po
+from payload_standalone import run, standalone  # noqa: F401  (standalone: a fixture)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CH, QU = po.CHUNK, po.QUARTER
 N = 6 * CH + QU + 3
 NS = [1, 8191, 8192, 8193, N]
@@ -225,49 +222,11 @@ def test_wire_from_host_raises_before_any_device_work(lib, monkeypatch):
 
 
 # ---- the same corpus through the sanitized stand-alone program --------------------------------
-def _compiler():
-    for c in ("c++", "g++", "clang++"):
-        if shutil.which(c):
-            return c
-    raise RuntimeError("no host C++ compiler")
-
-
-@pytest.fixture(scope="module")
-def standalone(tmp_path_factory):
-    """(path of the program, sanitized?): built with -fsanitize=address,undefined, or without
-    when the sanitizer runtime does not link on this machine."""
-    d = tmp_path_factory.mktemp("wire_validate")
-    exe = str(d / "wire_validate_main")
-    src = os.path.join(ROOT, "tests", "wire_validate_main.cc")
-    base = [_compiler(), "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", src, "-o", exe]
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"]
-    # the runtimes linked into the program itself where the compiler can (the program then starts
-    # whatever else the loader brings in first)
-    for extra in (["-static-libasan", "-static-libubsan"], ["-static-libsan"], []):
-        r = subprocess.run(base + san + extra, capture_output=True, text=True)
-        if r.returncode == 0:
-            return exe, True
-    print("sanitizer build failed, building without:\n" + r.stderr[-2000:])
-    subprocess.run(base, check=True)
-    return exe, False
-
-
 def test_the_corpus_through_the_sanitized_standalone_program(lib, standalone, tmp_path):
     exe, sanitized = standalone
     corpus = [(name, raw, n, None) for name, (raw, n) in sorted(accepted_payloads().items())]
     corpus += [(name,) + mutations()[name] for name in MUTATIONS]
-    lines = []
-    for i, (_, raw, n_expected, _) in enumerate(corpus):
-        path = tmp_path / f"payload_{i:03d}.bin"
-        path.write_bytes(raw)
-        lines.append(f"{n_expected} {path}")
-    (tmp_path / "list.txt").write_text("\n".join(lines) + "\n")
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, str(tmp_path / "list.txt")], capture_output=True, text=True, env=env)
-    assert r.returncode == 0, r.stderr[-4000:]
-    assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
-    verdicts = r.stdout.splitlines()
-    assert len(verdicts) == len(corpus)
+    verdicts = run(exe, ["wire"], tmp_path, corpus)
     for (name, raw, n_expected, want), got in zip(corpus, verdicts):
         rc, msg = validate(lib, raw, n_expected)
         assert got == ("OK" if rc == 0 else "BAD " + msg), name         # the library's verdict
@@ -278,6 +237,21 @@ def test_the_corpus_through_the_sanitized_standalone_program(lib, standalone, tm
     print(f"{len(corpus)} payloads, sanitized build: {sanitized}")
 
 
+def test_every_truncation_through_the_sanitized_standalone_program(standalone, tmp_path):
+    """Each valid payload of n <= 100 cut at every length 0 .. size, each prefix in a heap block of
+    exactly its length: only the whole payload is accepted and no read leaves a block."""
+    exe, sanitized = standalone
+    rng = np.random.default_rng(3)
+    corpus = [("n=1", accepted_payloads()["n=1"][0], 0)]
+    for n, E in ((1, 0), (7, 3), (64, 64), (100, 0), (100, 1), (100, 37)):
+        gidx = np.sort(rng.choice(n, E, replace=False)).astype(np.int64)
+        f = po.build_idxval(n, gidx, (np.arange(E) + 1).astype(np.float32), thresh=0, codec=po.CODEC_TOP, k=E)
+        corpus.append((f"n={n} E={E}", wm.pack(f), 0))
+    for (name, raw, _), got in zip(corpus, run(exe, ["wire", "--trunc"], tmp_path, corpus)):
+        assert got == f"TRUNC ok=1 of={len(raw) + 1}", (name, got)
+    print(f"{len(corpus)} payloads, sanitized build: {sanitized}")
+
+
 def test_the_readers_rules_on_the_corpus_through_the_sanitized_program(lib, standalone, tmp_path):
     """wire_accept and wire_clamp (fc_wire_host.h: what k_wire_unpack and the wire fold do with bytes
     nobody validated) on the same corpus, each payload in a heap block of exactly its length: the
@@ -285,18 +259,8 @@ def test_the_readers_rules_on_the_corpus_through_the_sanitized_program(lib, stan
     exe, sanitized = standalone
     corpus = [(name, raw, n) for name, (raw, n) in sorted(accepted_payloads().items())]
     corpus += [(name, mutations()[name][0], mutations()[name][1] or N) for name in MUTATIONS]
-    lines = []
-    for i, (_, raw, n) in enumerate(corpus):
-        path = tmp_path / f"payload_{i:03d}.bin"
-        path.write_bytes(raw)
-        lines.append(f"{n} {path}")
-    (tmp_path / "list.txt").write_text("\n".join(lines) + "\n")
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, "--clamp", str(tmp_path / "list.txt")], capture_output=True, text=True, env=env)
-    assert r.returncode == 0, r.stderr[-4000:]
-    assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
-    got = dict(zip((name for name, _, _ in corpus), r.stdout.splitlines()))
-    assert len(r.stdout.splitlines()) == len(corpus)
+    lines = run(exe, ["wire", "--clamp"], tmp_path, corpus)
+    got = dict(zip((name for name, _, _ in corpus), lines))
     for name, raw, n in corpus:
         # every payload: refused, or ranges inside [0, E) (the program checked them and read them)
         assert got[name] == "REJECT" or re.fullmatch(r"ACCEPT E=\d+ exact=[01]", got[name]), (name, got[name])

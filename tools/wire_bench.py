@@ -230,7 +230,7 @@ def main():
             for x in arrs:
                 assert lib.fc_wire_validate(ctypes.c_void_p(x.ctypes.data), x.size, n) == 0
             tv.append((time.perf_counter() - t0) * 1e3)
-            us, wires = timed(lambda: [codec._wire_upload(x, L.WireHdr.from_buffer_copy(x[:128].tobytes()), dev)
+            us, wires = timed(lambda: [codec.TOP.upload(x, L.WireHdr.from_buffer_copy(x[:128].tobytes()), dev)
                                        for x in arrs])
             th.append(us / 1e3)
             us, _ = timed(lambda: codec.unpack(wires, pk))

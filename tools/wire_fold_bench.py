@@ -189,7 +189,7 @@ def main():
             for x in arrs:
                 assert lib.fc_wire_validate(ctypes.c_void_p(x.ctypes.data), x.size, n) == 0
             tv.append((time.perf_counter() - t0) * 1e3)
-            us, wires = timed(lambda: [codec._wire_upload(x, L.WireHdr.from_buffer_copy(x[:128].tobytes()), dev,
+            us, wires = timed(lambda: [codec.TOP.upload(x, L.WireHdr.from_buffer_copy(x[:128].tobytes()), dev,
                                                           out=slab[int(o): int(o) + x.size])
                                        for x, o in zip(arrs, offs)])
             th.append(us / 1e3)
